@@ -12,7 +12,9 @@ clean wav -> masked log-L1 loss.  Weights: seeded random at the real sizes (no c
 Multi-GPU: utterances shard data-parallel with NO data-path collective (inference); every rank runs
 the same per-GPU batch ("weak" scaling); value = all utterances / max-over-ranks time.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3       set up, warm up, time the steps, print the line: nothing else runs
+    python bench.py ... --full              + the side legs as extra keys of the line (roofline, host-fed, parity-mode rates, CPU baseline)
+    python bench.py ... --dump-outputs DIR  + the last timed step's outputs as DIR/<name>.npy (same arguments -> same inputs, run to run)
     python bench.py --gpus N ...            (no torchrun environment: starts the N ranks itself, see launch_ranks())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Prints ONE JSON line on rank 0 (`n_gpus` = the world size the ranks OBSERVED through the collective, checked against --gpus).
@@ -433,6 +435,7 @@ def build_stub_workload(args, ranks):
     lens = torch.randint(1, F + 1, (B,), generator=g)
     w = {'lib': None, 'collective': args.workload in ('finetune', 'lstm'), 'max_len': F, 'wavs': feats, 'lengths': lens, 'dtype': 'f32'}
     if not w['collective']:
+        torch.manual_seed(0)
         lin = torch.nn.Linear(D, N)
 
         def step(feats, lens, max_len):
@@ -567,6 +570,29 @@ def host_fed_leg(args, w, dev):
     return rec
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000      # --dump-outputs: all files together stay under 64 MB
+
+
+def snapshot_outputs(named):
+    """Host float32 copies of what the last timed step returned (taken before anything else runs the step again)."""
+    return {name: t.detach().to('cpu', torch.float32).numpy().copy() for name, t in named if torch.is_tensor(t)}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy per output of the timed path.  An array above its share of the budget is written as a fixed sample:
+    the flattened elements at the sorted indices numpy's default_rng(0) draws without replacement (the same indices in every run and build)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    if sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def head_pass_bytes(head_feat):
     """algorithmic HBM bytes per utterance of the head pass: the sum over its kernels, and the fully fused bound"""
     T, F, K = 160000, 1001, 201
@@ -622,6 +648,10 @@ def main():
     ap.add_argument('--head-feat', choices=tuple(HEAD_FEATS), default='mel120', help='head workload: the mask head\'s input features')
     ap.add_argument('--streams', type=int, default=1, help='process the batch as this many sub-batches on separate HIP streams (enhance workload)')
     ap.add_argument('--graph', action='store_true', help='replay the pass as one hipGraph launch (serving-size batches are launch-bound)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also run the side legs and report them as extra keys of the line: the roofline '
+                                                        'leg, the host-fed rate, the parity-mode / batch-12 rates, the CPU baseline (each has a --no-... switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned (rank 0) as DIR/<name>.npy, float32, '
+                                                                        'at most 64 MB in all (a fixed seeded sample of a larger array)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-host-fed', action='store_true', help='skip the PCIe-inclusive side measurement')
@@ -657,16 +687,18 @@ def main():
     ranks.sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        wav_pred, loss, _ = step(wavs, lengths, max_len)
+        wav_pred, loss, aux = step(wavs, lengths, max_len)
     ranks.local_sync()
     elapsed = time.perf_counter() - t0
     if ranks.distributed:
         ranks.dist.barrier()
     elapsed = ranks.max_over_ranks(elapsed)
     assert torch.isfinite(wav_pred).all() and torch.isfinite(loss)
+    # what a caller of the timed path receives: the enhanced waveforms, the loss and the predicted spectrum (the training steps return the loss alone)
+    dumped = snapshot_outputs((('wav_pred', None if w['collective'] else wav_pred), ('loss', loss), ('predicted', aux))) if args.dump_outputs else None
 
-    do_roofline = not args.no_roofline and lib is not None
-    if not args.no_roofline:
+    do_roofline = args.full and not args.no_roofline and lib is not None
+    if args.full and not args.no_roofline:
         # roofline leg: the same K steps with HIP events recorded (in-library, on the launch stream) around every kernel of the dominant
         # families.  EVERY rank runs it (the training steps all-reduce; and no rank-conditional code may sit between two collectives).
         if lib is not None:
@@ -735,7 +767,10 @@ def main():
     if do_roofline:
         roofline_report(args, lib, out)
 
-    if not args.stub_step:
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
+
+    if args.full and not args.stub_step:
         if args.workload in ('enhance', 'head') and not args.graph and not args.no_host_fed:
             out['host_fed'] = host_fed_leg(args, w, dev)
         if not args.no_extras:

@@ -1,7 +1,7 @@
 """CPU oracle for the speech-enhancement hot path.
 
 THIS PACKAGE IS TEST INFRASTRUCTURE, NOT PRODUCT CODE.
-Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import it, and
+Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py --full``'s ``cpu_baseline`` leg may import it, and
 only as the checker / the reported CPU baseline.  Nothing under ``speech-enhancement-by-s3prl_amd/`` imports
 it; the product path fails loudly if the HIP extension is missing.
 

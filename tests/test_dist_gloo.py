@@ -139,7 +139,7 @@ def test_bench_control_flow_two_ranks_stubbed(workload, world):
     2-rank fine-tune rehearsal deadlocked because rank 0 alone re-ran all-reducing steps; this is the test that would have caught it
     (a hang here fails by timeout)."""
     import json
-    out = _run_bench(['--gpus', str(world), '--workload', workload, '--stub-step', '--backend', 'gloo', '--steps', '3', '--warmup', '1'], timeout=240)
+    out = _run_bench(['--gpus', str(world), '--workload', workload, '--stub-step', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--full'], timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines

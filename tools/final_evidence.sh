@@ -22,7 +22,7 @@ fi
 if [ "$part" != 3 ]; then      # part 3: only what follows the side-workload lines (re-run after a failure further down)
 tools/collect_profiles.sh $tag _finetune --workload finetune
 cd "$root"
-python3 bench.py --workload lstm --no-cpu-baseline > "$out/${tag}_lstm_bench.json" 2> "$out/lstm.err"
+python3 bench.py --full --workload lstm --no-cpu-baseline > "$out/${tag}_lstm_bench.json" 2> "$out/lstm.err"
 python3 tools/bench_kernels.py mhsa_train > "$out/${tag}_mhsa_train.txt" 2>&1
 python3 tools/bench_kernels.py mhsa_peaked > "$out/${tag}_mhsa_peaked.txt" 2>&1
 fi
