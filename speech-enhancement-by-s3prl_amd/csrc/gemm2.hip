@@ -14,6 +14,7 @@
 #include "common.h"
 #include "bf16.h"
 #include "prof.h"
+#include "gemm_launch.h"
 
 // The raised wave priority around the MFMA clusters (s_setprio 1 ... 0) is OFF: A/B on one box, fine-tune step 19.73 -> 19.52 ms without it
 // (the same finding as for the row-complete and the persistent kernels).  SE_AMD_EXTRA_DEFINES=-DSE_AMD_SETPRIO python build.py --force brings it back.
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(128 * WR) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
-  int tm, tn;          // grouped order inside the XCD's id range (see gemm3.hip)
+  int tm, tn;          // grouped order inside the XCD's id range (see gemm6.hip)
   {
     const int per_group = group_m * tiles_n, grp = id / per_group, first_m = grp * group_m;
     const int gsz = min(tiles_m - first_m, group_m), in = id - grp * per_group;
@@ -337,7 +338,6 @@ __global__ __launch_bounds__(128 * WR) __attribute__((amdgpu_waves_per_eu(2, 2))
 }  // namespace se
 
 // internal launcher (gemm.hip's se_gemm_bf16 dispatches here); arguments already validated.
-// variant: 2 = 256x128 lockstep, 3 = 256x128 ping-pong, 4 = 128x128 two-workgroups-per-CU
 namespace {
 struct GArgs {
   const uint16_t* A; int lda; const uint16_t* W; int ldw; const float* bias; const float* residual; int M, N, K, act;
@@ -376,23 +376,19 @@ int launch_cfg(const GArgs& g) {
 }
 }  // namespace
 
-extern "C" int se_gemm2_launch(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* residual_f32,
-                               int M, int N, int K, int act, uint16_t* out_bf16, float* out_f32, int ldc, int vec_ok, int variant, void* stream) {
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = getenv("SE_AMD_GEMM_DBG");     // developer ablation switch (timing only, wrong results)
-    dbg = e ? atoi(e) : 0;
-  }
-  static int group_m = 0;
-  if (group_m == 0) {
-    const char* gm = getenv("SE_AMD_GEMM_GROUPM2");
-    group_m = gm ? atoi(gm) : 1;
-    if (group_m < 1) group_m = 1;
-  }
-  GArgs g{A, lda, W, ldw, bias, residual_f32, M, N, K, act, out_bf16, out_f32, ldc, vec_ok, dbg, se::as_stream(stream), group_m, 1, 0};
-  se::ProfScope prof(se::kProfGemm, 2.0 * M * (double)N * K, g.st);
-  if (variant == 4) return launch_cfg<2, 2, 0>(g);
-  if (variant == 3 && K >= 2 * se::k2BK) return launch_cfg<4, 3, 1>(g);
+int se::launch_gemm2(const GemmArgs& a, GemmRoute route) {
+  const GemmCall c = gemm_call_of(a);
+  const bool mine = route == GemmRoute::Tile128x2 || route == GemmRoute::PingPong256x128 || route == GemmRoute::Lockstep256x128;
+  SE_REQUIRE(mine && gemm_route_ok(route, c), "launch_gemm2: route %d does not take this call (M=%d N=%d K=%d)", (int)route, a.M, a.N, a.K);
+#ifdef SE_AMD_STAMPS
+  static const int dbg = getenv("SE_AMD_GEMM_DBG") ? atoi(getenv("SE_AMD_GEMM_DBG")) : 0;     // developer ablation switch (timing only, wrong results)
+#else
+  constexpr int dbg = 0;
+#endif
+  GArgs g{a.A, a.lda, a.W, a.ldw, a.bias, a.residual, a.M, a.N, a.K, a.act, a.out_bf16, a.out_f32, a.ldc, c.vec_ok, dbg, a.st, gemm_tuning().group_m2, 1, 0};
+  ProfScope prof(kProfGemm, 2.0 * a.M * (double)a.N * a.K, g.st);
+  if (route == GemmRoute::Tile128x2) return launch_cfg<2, 2, 0>(g);
+  if (route == GemmRoute::PingPong256x128) return launch_cfg<4, 3, 1>(g);
   return launch_cfg<4, 3, 0>(g);
 }
 

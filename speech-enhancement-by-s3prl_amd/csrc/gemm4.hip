@@ -23,6 +23,7 @@
 #include "bf16.h"
 #include "prof.h"
 #include "encoder_impl.h"
+#include "gemm_launch.h"
 
 SE_CLKPROBE_DECL(clkprobe_gemm7)
 // -DSE7_ABL=<mask> (gemm7_res_ln_kernel, timing only, results wrong): 1 no LDS-DMA, 2 no s_barrier in the K loop, 4 no LDS fragment reads, 8 no epilogue
@@ -225,7 +226,7 @@ __device__ __forceinline__ void ln_epilogue4(f32x4 (&acc)[4][12], char* smem, in
       }
       if (!ROUT && ok && out_f32) *reinterpret_cast<float4*>(out_f32 + o + 16 * t) = make_float4(y0, y1, y2, y3);
       if (out_bf16) {
-        // 16-B bf16 stores (as gemm3.hip): lanes l, l ^ 16 trade 4-column pieces of the MFMA tile pair (t - 1, t), so a lane owns 8
+        // 16-B bf16 stores: lanes l, l ^ 16 trade 4-column pieces of the MFMA tile pair (t - 1, t), so a lane owns 8
         // consecutive columns and one wave instruction writes 16 rows x 64 contiguous bytes instead of 16 x 32
         const uint2 pk = make_uint2(pack_bf16x2(y0, y1), pack_bf16x2(y2, y3));
         if (ROUT)      // tile-major lo bytes: rows past M are written too (the buffer covers whole tiles) and never read as real rows
@@ -726,11 +727,13 @@ static int gemm4_launch(const uint16_t* A, int lda, const uint16_t* W, int ldw, 
 
 // The row-complete kernel WITHOUT its LayerNorm (round 4): out = A[M,K] . W[768,K]^T (+ bias) (+ residual_f32) as fp32 and / or bf16 rows.  For N = 768
 // the 256 x 256-tile kernels run 378 tiles = a second round filled to 48 %; 251 row tiles of 128 x 768 are one full round.  Called by se_gemm_bf16
-// (csrc/gemm.hip) for the training path's FFN-output forward and the FFN1 / QKV input gradients (K = 3072 / 2304).  Returns 1 when the shape is not its own.
+// (csrc/gemm.hip) for the training path's FFN-output forward and the FFN1 / QKV input gradients (K = 3072 / 2304).  A call outside
+// gemm_row_complete768_ok (gemm_route.h) is an error.
 extern "C" int se_gemm7_plain_launch(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* residual_f32, int M, int K,
                                      uint16_t* out_bf16, float* out_f32, void* stream) {
-  if (!(K % 64 == 0 && K >= 128 && (size_t)M * lda < (1u << 31) && (size_t)se::k4N * ldw < (1u << 31))) return 1;
-  if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)residual_f32 | (uintptr_t)out_f32 | (uintptr_t)out_bf16 | (uintptr_t)bias) % 16) != 0) return 1;
+  SE_REQUIRE(A && W && (out_bf16 || out_f32) && M > 0, "se_gemm7_plain_launch: null argument");
+  const se::GemmArgs g{A, lda, W, ldw, bias, residual_f32, M, se::k4N, K, SE_ACT_IDENTITY, out_bf16, out_f32, se::k4N, se::as_stream(stream)};
+  SE_REQUIRE(se::gemm_row_complete768_ok(se::gemm_call_of(g)), "se_gemm7_plain_launch: K=%d must be a multiple of 64 (>= 128), 31-bit operand offsets, 16-B aligned pointers", K);
   static bool attr_set = false;
   if (!attr_set) {
     SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm7_res_ln_kernel<0, 0, 0, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k7Lds));

@@ -1,7 +1,7 @@
 // gemm6.hip -- 256 x 256 bf16 GEMM, 64-deep K-tiles, eight phases per pair of K-tiles (C = epilogue(A . W^T + bias); contract: gemm.hip)
 //
-// Why another main loop: gemm3's 32-deep K-steps stage rows of 64 B, so every LDS-DMA wave instruction touches 16 cache lines and uses
-// half of each (the "fragment-shaped load" of the CDNA guide: twice the TA work per byte), and the whole family sat at ~0.9 PFLOP/s at
+// Why another main loop: the first 256 x 256 kernel (gemm3, retired: DESIGN "retired kernels") staged 32-deep K-steps in rows of 64 B,
+// so every LDS-DMA wave instruction touches 16 cache lines and uses half of each (the "fragment-shaped load" of the CDNA guide: twice the TA work per byte), and the whole family sat at ~0.9 PFLOP/s at
 // 4096^3 / 8192^3 where the guide's 256^2 eight-phase structure reaches 1.3-1.5 on the same chip.  This kernel is that structure:
 //
 //   tile     : 256 x 256 x 64; 512 threads = 8 waves as 2 (M) x 4 (N), wave tile 128 x 64 = 8 x 4 v_mfma_f32_16x16x32_bf16 tiles
@@ -17,12 +17,13 @@
 //                phase 1 of tile t : B_0 (t+1)     phase 2 : A_0 (t+2)     phase 3 : B_1 (t+2)     phase 4 : A_1 (t+2)
 //              The only wait of a K-tile is vmcnt(6) in phase 4 (three half-tiles stay in flight): in-order retirement then guarantees
 //              every half-tile of tile t+1; it is read from the next phase on (one barrier later for the lagging wave group).
-//   epilogue : gemm3's (swapped operands, C^T accumulators, 16-B stores, bias / GELU / fp32 residual fused, compile-time specialised)
+//   epilogue : gemm2.hip's (swapped operands, C^T accumulators, 16-B stores, bias / GELU / fp32 residual fused, compile-time specialised)
 #include "clkprobe.h"
 #include <stdlib.h>
 #include "common.h"
 #include "bf16.h"
 #include "prof.h"
+#include "gemm_launch.h"
 
 SE_CLKPROBE_DECL(clkprobe_gemm6)
 namespace se {
@@ -124,7 +125,7 @@ typedef unsigned int se6_u32x4 __attribute__((ext_vector_type(4)));
     if constexpr (OBF) {                                                                                                   \
       if (!(PRED)) {                                                                                                       \
         /* 16-B stores: lanes l, l ^ 16 trade 4-column pieces of two neighbouring MFMA tiles, so each lane owns 8 consecutive   \
-           bf16 columns and a wave instruction writes 16 rows x 64 contiguous bytes (gemm3.hip); X3: the y1 slice twice, then y2 */ \
+           bf16 columns and a wave instruction writes 16 rows x 64 contiguous bytes; X3: the y1 slice twice, then y2 */ \
         _Pragma("unroll") for (int sl = 0; sl < (X3 ? 3 : DUAL ? 2 : 1); ++sl) {                                           \
           _Pragma("unroll") for (int p2 = 0; p2 < 2; ++p2) {                                                               \
             const bool second = (X3 && sl == 2) || (DUAL && sl == 1);                                                      \
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(k6Threads) __attribute__((amdgpu_waves_per_eu(2, 2)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
 
-  // XCD-aware bijective remap + grouped order (as gemm3): each XCD walks a contiguous id range, GROUP_M tile rows swept n-major
+  // XCD-aware bijective remap + grouped order: each XCD walks a contiguous id range, GROUP_M tile rows swept n-major
   const int nwg = tiles_m * tiles_n;
   int id;
   {
@@ -615,138 +616,81 @@ __global__ __launch_bounds__(k6Threads) __attribute__((amdgpu_waves_per_eu(2, 2)
 }  // namespace se
 
 namespace {
-struct G6Args {
-  const uint16_t* A; int lda; const uint16_t* W; int ldw; const float* bias; const float* residual; int M, N, K;
-  uint16_t* out_bf16; float* out_f32; int ldc; hipStream_t st;
-};
+using se::GemmArgs;
 
-template <int ACT, int EF>
-int launch6(const G6Args& g) {
-  const int tiles_m = (g.M + se::k6BM - 1) / se::k6BM, tiles_n = (g.N + se::k6BN - 1) / se::k6BN;
-  static int group_m = 0;
+struct G6Params { int group_m, late_start, n_cu; };
+
+// What every launcher of this file needs besides its arguments: the kernel's dynamic-LDS limit raised (once per instantiation), the tile-group
+// height and staggered start (gemm_tuning()), and the CU count (once: one workgroup per CU, a multiple of the 8 XCDs).
+template <auto Kernel>
+int g6_prepare(int max_lds, G6Params& p) {
   static bool attr_set = false;
   if (!attr_set) {
-    const char* gm = getenv("SE_AMD_GEMM_GROUPM");
-    group_m = gm ? atoi(gm) : 4;
-    if (group_m < 1) group_m = 1;
-    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm6_bf16_kernel<ACT, EF>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k6Lds));
+    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     attr_set = true;
   }
-  hipLaunchKernelGGL((se::gemm6_bf16_kernel<ACT, EF>), dim3(tiles_m * tiles_n), dim3(se::k6Threads), se::k6Lds, g.st, g.A, g.lda, g.W, g.ldw,
-                     g.bias, g.residual, g.M, g.N, g.K, g.out_bf16, g.out_f32, g.ldc, tiles_m, tiles_n, group_m);
-  SE_LAUNCH_CHECK();
-  return SE_OK;
-}
-}  // namespace
-
-namespace {
-template <int ACT>
-int launch6p(const G6Args& g) {
-  const int tiles_m = (g.M + se::k6BM - 1) / se::k6BM, tiles_n = g.N / se::k6BN;
-  static int group_m = 0, n_cu = 0, late_start = 0;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const char* gm = getenv("SE_AMD_GEMM_GROUPM");
-    group_m = gm ? atoi(gm) : 4;
-    if (group_m < 1) group_m = 1;
-    const char* ls = getenv("SE_AMD_GEMM6P_LATE");
-    late_start = ls ? atoi(ls) : 2;
-    if (const char* sk = getenv("SE_AMD_GEMM6P_SKEW")) late_start |= (atoi(sk) & 0xff) << 8;
+  static int n_cu = 0;
+  if (n_cu == 0) {
     int dev = 0;
     hipDeviceProp_t prop;
     SE_HIP(hipGetDevice(&dev));
     SE_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount & ~7;          // one workgroup per CU, a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
-    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm6p_bf16_kernel<ACT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k6Lds + 32768));
-    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm6p_bf16_kernel<ACT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k6Lds + 32768));
-    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm6p_bf16_kernel<ACT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k6Lds + 32768));
-    attr_set = true;
+    n_cu = std::max(prop.multiProcessorCount & ~7, 8);
   }
-  static int inm = -1;
-  // 0: the first form (DMA issue in the read section, raised wave priority around the MFMA groups); 1: DMA issue between the MFMA groups
-  // (A/B: tie); 2 (default): the first form without the priority change (A/B, whole step: 4.018 -> 4.003 ms)
-  if (inm < 0) { const char* e = getenv("SE_AMD_GEMM6P_INM"); inm = e ? atoi(e) : 2; }
-  const int grid = std::min(n_cu, (tiles_m * tiles_n + 7) & ~7);
-  if (inm == 2)
-    hipLaunchKernelGGL((se::gemm6p_bf16_kernel<ACT, 2>), dim3(grid), dim3(se::k6Threads), se::k6Lds + g.N * 4, g.st, g.A, g.lda, g.W, g.ldw, g.bias, g.M, g.N,
-                       g.K, g.out_bf16, g.ldc, tiles_m, tiles_n, group_m, late_start, 0LL);
-  else if (inm)
-    hipLaunchKernelGGL((se::gemm6p_bf16_kernel<ACT, 1>), dim3(grid), dim3(se::k6Threads), se::k6Lds + g.N * 4, g.st, g.A, g.lda, g.W, g.ldw, g.bias, g.M, g.N,
-                       g.K, g.out_bf16, g.ldc, tiles_m, tiles_n, group_m, late_start, 0LL);
-  else
-    hipLaunchKernelGGL((se::gemm6p_bf16_kernel<ACT, 0>), dim3(grid), dim3(se::k6Threads), se::k6Lds + g.N * 4, g.st, g.A, g.lda, g.W, g.ldw, g.bias, g.M, g.N,
-                       g.K, g.out_bf16, g.ldc, tiles_m, tiles_n, group_m, late_start, 0LL);
+  p = G6Params{se::gemm_tuning().group_m, se::gemm_tuning().late_start, n_cu};
+  return SE_OK;
+}
+
+template <int ACT, int EF>
+int launch6(const GemmArgs& g) {
+  const int tiles_m = (g.M + se::k6BM - 1) / se::k6BM, tiles_n = (g.N + se::k6BN - 1) / se::k6BN;
+  G6Params p;
+  if (const int rc = g6_prepare<se::gemm6_bf16_kernel<ACT, EF>>(se::k6Lds, p)) return rc;
+  hipLaunchKernelGGL((se::gemm6_bf16_kernel<ACT, EF>), dim3(tiles_m * tiles_n), dim3(se::k6Threads), se::k6Lds, g.st, g.A, g.lda, g.W, g.ldw,
+                     g.bias, g.residual, g.M, g.N, g.K, g.out_bf16, g.out_f32, g.ldc, tiles_m, tiles_n, p.group_m);
+  SE_LAUNCH_CHECK();
+  return SE_OK;
+}
+
+// the persistent kernel in its default form (INM = 2: DMA issue in the read section, no wave-priority change); DUAL: gelu of the bf16-rounded
+// rows as a second output `dual_off` elements behind out_bf16
+template <int ACT, int DUAL>
+int launch6p(const GemmArgs& g, long long dual_off) {
+  const int tiles_m = (g.M + se::k6BM - 1) / se::k6BM, tiles_n = g.N / se::k6BN;
+  G6Params p;
+  if (const int rc = g6_prepare<se::gemm6p_bf16_kernel<ACT, 2, DUAL>>(se::k6Lds + 32768, p)) return rc;
+  const int grid = std::min(p.n_cu, (tiles_m * tiles_n + 7) & ~7);
+  hipLaunchKernelGGL((se::gemm6p_bf16_kernel<ACT, 2, DUAL>), dim3(grid), dim3(se::k6Threads), se::k6Lds + g.N * 4, g.st, g.A, g.lda, g.W, g.ldw, g.bias,
+                     g.M, g.N, g.K, g.out_bf16, g.ldc, tiles_m, tiles_n, p.group_m, p.late_start, dual_off);
   SE_LAUNCH_CHECK();
   return SE_OK;
 }
 }  // namespace
 
-// returns 1 if this kernel does not handle the call (caller falls back to gemm3 / gemm2), 0 on success, < 0 on error
-extern "C" int se_gemm6_launch(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* residual_f32,
-                               int M, int N, int K, int act, uint16_t* out_bf16, float* out_f32, int ldc, int vec_ok, void* stream) {
-  const bool vec = vec_ok && (N % 4 == 0) && (ldc % 4 == 0);
-  const bool one_out = (out_bf16 != nullptr) != (out_f32 != nullptr);
-  if (!vec || !one_out || K % se::k6BK != 0 || K < 2 * se::k6BK || (act != SE_ACT_IDENTITY && act != SE_ACT_GELU)) return 1;
-  G6Args g{A, lda, W, ldw, bias, residual_f32, M, N, K, out_bf16, out_f32, ldc, se::as_stream(stream)};
-  const bool gelu = act == SE_ACT_GELU, res = residual_f32 != nullptr, obf = out_bf16 != nullptr;
-  se::ProfScope prof(se::kProfGemm, 2.0 * M * (double)N * K, g.st);
-  static int persistent = -1;
-  if (persistent < 0) {
-    const char* e = getenv("SE_AMD_GEMM6P");          // 0: one workgroup per tile for every shape
-    persistent = e ? atoi(e) : 1;
-  }
-  // persistent form: bf16 output without residual, several tiles per CU, whole column tiles, an even number of K-tiles, 32-bit source offsets
-  if (persistent && obf && !res && N % se::k6BN == 0 && N <= 8192 && (K / se::k6BK) % 2 == 0 && K >= 4 * se::k6BK && (ldc % 8) == 0 &&
-      ((uintptr_t)out_bf16 % 16) == 0 && (size_t)M * lda < (1u << 31) && (size_t)N * ldw < (1u << 31) &&
-      (size_t)((M + se::k6BM - 1) / se::k6BM) * (N / se::k6BN) > 256)
-    return gelu ? launch6p<SE_ACT_GELU>(g) : launch6p<SE_ACT_IDENTITY>(g);
-  if (!gelu && !res && obf) return launch6<SE_ACT_IDENTITY, 2>(g);
-  if (gelu && !res && obf) return launch6<SE_ACT_GELU, 2>(g);
-  if (!gelu && res && !obf) return launch6<SE_ACT_IDENTITY, 4 | 1>(g);
-  if (!gelu && !res && !obf) return launch6<SE_ACT_IDENTITY, 4>(g);
-  if (gelu && !res && !obf) return launch6<SE_ACT_GELU, 4>(g);
-  return 1;
+int se::launch_gemm6(const GemmArgs& g, GemmRoute route) {
+  const bool mine = route == GemmRoute::Persistent256 || route == GemmRoute::Tile256;
+  SE_REQUIRE(mine && gemm_route_ok(route, gemm_call_of(g)), "launch_gemm6: route %d does not take this call (M=%d N=%d K=%d)", (int)route, g.M, g.N, g.K);
+  const bool gelu = g.act == SE_ACT_GELU, res = g.residual != nullptr, obf = g.out_bf16 != nullptr;
+  ProfScope prof(kProfGemm, 2.0 * g.M * (double)g.N * g.K, g.st);
+  if (route == GemmRoute::Persistent256) return gelu ? launch6p<SE_ACT_GELU, 0>(g, 0LL) : launch6p<SE_ACT_IDENTITY, 0>(g, 0LL);
+  // gemm_tile256_ok: one output; a residual only with identity -> fp32
+  if (res) return launch6<SE_ACT_IDENTITY, 4 | 1>(g);
+  if (obf) return gelu ? launch6<SE_ACT_GELU, 2>(g) : launch6<SE_ACT_IDENTITY, 2>(g);
+  return gelu ? launch6<SE_ACT_GELU, 4>(g) : launch6<SE_ACT_IDENTITY, 4>(g);
 }
 
 // y = A . W^T + bias as bf16 rows at out_pre AND gelu(y) (erf form, of the bf16-rounded y) at out_act, one launch of the persistent kernel: the
 // training forward of the FFN's first projection, which keeps the pre-activation for the backward pass (encoder_train.hip; was se_gemm_bf16 +
-// se_gelu_bf16).  Returns 1 when the shape is not the persistent kernel's (the caller then runs the two launches).
+// se_gelu_bf16).  Returns 1 when the shape is not the persistent kernel's or SE_AMD_GEMM6_DUAL=0 (the caller then runs the two launches).
 extern "C" int se_gemm6_dual_gelu_launch(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, int M, int N, int K, uint16_t* out_pre,
                                          uint16_t* out_act, int ldc, void* stream) {
-  if (!(N % se::k6BN == 0 && N <= 8192 && K % se::k6BK == 0 && (K / se::k6BK) % 2 == 0 && K >= 4 * se::k6BK && (ldc % 8) == 0 && ldc >= N &&
-        lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && (size_t)M * lda < (1u << 31) && (size_t)N * ldw < (1u << 31) &&
-        (size_t)((M + se::k6BM - 1) / se::k6BM) * (N / se::k6BN) > 256 &&
+  if (!(se::gemm_persistent256_shape_ok(M, N, K, lda, ldw, ldc) && ldc >= N && lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 &&
         (((uintptr_t)A | (uintptr_t)W | (uintptr_t)out_pre | (uintptr_t)out_act | (uintptr_t)bias) % 16) == 0))
     return 1;
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("SE_AMD_GEMM6_DUAL"); on = e ? atoi(e) : 1; }      // A/B: 0 = two launches
-  if (!on) return 1;
-  const int tiles_m = (M + se::k6BM - 1) / se::k6BM, tiles_n = N / se::k6BN;
-  static int group_m = 0, n_cu = 0, late_start = 0;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const char* gm = getenv("SE_AMD_GEMM_GROUPM");
-    group_m = gm ? atoi(gm) : 4;
-    if (group_m < 1) group_m = 1;
-    const char* ls = getenv("SE_AMD_GEMM6P_LATE");
-    late_start = ls ? atoi(ls) : 2;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    SE_HIP(hipGetDevice(&dev));
-    SE_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount & ~7;
-    if (n_cu < 8) n_cu = 8;
-    SE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(se::gemm6p_bf16_kernel<SE_ACT_IDENTITY, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, se::k6Lds + 32768));
-    attr_set = true;
-  }
-  hipStream_t st = se::as_stream(stream);
-  se::ProfScope prof(se::kProfGemm, 2.0 * M * (double)N * K, st);
-  const int grid = std::min(n_cu, (tiles_m * tiles_n + 7) & ~7);
-  hipLaunchKernelGGL((se::gemm6p_bf16_kernel<SE_ACT_IDENTITY, 2, 1>), dim3(grid), dim3(se::k6Threads), se::k6Lds + N * 4, st, A, lda, W, ldw, bias, M, N, K, out_pre,
-                     ldc, tiles_m, tiles_n, group_m, late_start, (long long)(out_act - out_pre));
-  SE_LAUNCH_CHECK();
-  return SE_OK;
+  if (!se::gemm_tuning().dual) return 1;
+  const GemmArgs g{A, lda, W, ldw, bias, nullptr, M, N, K, SE_ACT_IDENTITY, out_pre, nullptr, ldc, se::as_stream(stream)};
+  se::ProfScope prof(se::kProfGemm, 2.0 * M * (double)N * K, g.st);
+  return launch6p<SE_ACT_IDENTITY, 1>(g, (long long)(out_act - out_pre));
 }
 
 // out3 (M, 3 Kp) bf16 = the three-term activation operand [y1 | y1 | y2] of y = act(A . W^T + bias) (se_split3_bf16's layout, which = 0): the bf16x3
@@ -761,7 +705,7 @@ extern "C" int se_gemm_x3out_bf16(const uint16_t* A, int lda, const uint16_t* W,
   SE_REQUIRE(Kp == N && Kp % 8 == 0 && lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0, "se_gemm_x3out_bf16: bad leading dimensions (Kp must equal N = %d)", N);
   SE_REQUIRE((((uintptr_t)A | (uintptr_t)W | (uintptr_t)out3 | (uintptr_t)bias) % 16) == 0, "se_gemm_x3out_bf16: operands must be 16-B aligned");
   SE_REQUIRE(act == SE_ACT_IDENTITY || act == SE_ACT_GELU, "se_gemm_x3out_bf16: act %d (identity or GELU)", act);
-  G6Args g{A, lda, W, ldw, bias, nullptr, M, N, K, out3, nullptr, 3 * Kp, se::as_stream(stream)};
+  const GemmArgs g{A, lda, W, ldw, bias, nullptr, M, N, K, act, out3, nullptr, 3 * Kp, se::as_stream(stream)};
   se::ProfScope prof(se::kProfGemm, 2.0 * M * (double)N * K, g.st);
   return act == SE_ACT_GELU ? launch6<SE_ACT_GELU, 2 | 8>(g) : launch6<SE_ACT_IDENTITY, 2 | 8>(g);
 }

@@ -1,14 +1,17 @@
 // head.hip -- rows C1 / C2: LinearResidual.forward (model.py:28-34) and Linear.forward (model.py:14-17):
 //   [CMVN over time] -> x W^T + b -> activation -> [ (.) noisy power ]
-// fused into one pass over the features, in EXACT fp32 (v_mfma_f32_32x32x2_f32 == k-ordered fmaf chain).
+// fused into one pass over the features, to fp32 accuracy on the bf16 matrix instruction (three-term operand split, below).
 //
-//   colstats : per (utterance, feature dim) mean and unbiased std over time, exact two-pass
-//   head     : workgroup = 128 frames x all N outputs; 4 waves, wave w owns frames [32w, 32w+32) and
-//              keeps NT = ceil(N/32) accumulator tiles (7 for N = 201).  K is walked in chunks of 40
-//              through LDS: normalised feature tile [128][41] and weight chunk [NT*32][41] (odd pitch ->
-//              conflict-free ds_read_b32 operand fetches).
-// Bound: HBM (4*F*(D + 2N) bytes per utterance, +4*F*N when `offset` is stored); the f32 MFMA rate
-// (157 TF) puts the GEMM itself at about the same time, so the kernel is balanced, not MFMA-bound.
+//   colstats : per (utterance, feature dim) mean and unbiased std over time, one pass with fp64 sums
+//   split_w  : W (N, D) fp32 -> three bf16 planes, chunk-major (once per call, or once per model: se_head_split_weights_f32)
+//   head3    : workgroup = 128 frames x all N outputs; 4 waves, wave w owns frames [32w, 32w+32) and keeps NT = ceil(N/32) accumulator
+//              tiles of v_mfma_f32_32x32x16_bf16 (7 for N = 201).  K is walked in 16-k chunks through LDS: weights by LDS-DMA one chunk
+//              ahead, features (CMVN applied, then split) through registers, one barrier per chunk.  Any N <= 256, any activation.
+//   head5    : head3 without its control flow, for the shapes the evaluate()-style pass runs (N in (192, 224], sigmoid / ReLU at compile
+//              time, F >= 128), optionally with the SI-SDR sums taken in the epilogue.  SE_AMD_HEAD5=0 sends every call to head3.
+//   epilogue : (both) a wave's 32 x N outputs are one contiguous span of the row-major (M, N) tensors, so the activated mask goes through LDS
+//              in that layout, 8 rows at a time, and leaves as aligned 16-B stores with the noisy power read the same way.
+// Bound: HBM (4*F*(D + 2N) bytes per utterance, +4*F*N when `offset` is stored).
 #include <stdlib.h>
 #include <algorithm>
 #include "common.h"
@@ -70,172 +73,17 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
 }
 
 constexpr int kHM = 128;     // frames per workgroup
-// LDS footprint = occupancy: K chunks of 40 with 16-row epilogue passes are 57.7 KB (2 workgroups per CU); chunks of 20 with 8-row passes are
-// 29.6 KB, and the 168 registers of the N = 201 instantiation then allow 3 workgroups per CU: 328 -> 307 us (D = 120), 460 -> 419 us (D = 201)
-// per launch at B = 256 (tools/head_occ.sh; either change alone does nothing)
-#ifndef SE_HEAD_HK
-#define SE_HEAD_HK 20
-#endif
+// rows of a wave's 32 that go out per epilogue pass (16 or 8).  LDS footprint = occupancy: 8-row passes keep the epilogue slab below the staging
+// buffers
 #ifndef SE_HEAD_HALF
 #define SE_HEAD_HALF 8
 #endif
-constexpr int kHK = SE_HEAD_HK;      // K chunk (kHK / 4 16-B pieces per row)
-constexpr int kHP = kHK + 1; // LDS pitch (odd: conflict-free ds_read_b32 operand fetches)
-constexpr int kHHalf = SE_HEAD_HALF;   // rows of a wave's 32 that go out per epilogue pass (16 or 8)
-
-// Round 3 rewrite (the first version staged every element with its own index division and 4-B accesses and stored the outputs as 128-B row
-// pieces straight from the accumulator layout: 787 us for 256 utterances, 0.12 of the HBM rate).  Now:
-//   staging  : 16-B global loads (features: CMVN applied on the way; weights), no per-element division; LDS keeps the odd pitch
-//   epilogue : a wave's 32 x N outputs are ONE contiguous span of the row-major (M, N) tensors (N is the whole row), so the activated mask goes
-//              through LDS in that layout, 16 rows at a time, and leaves as aligned 16-B stores with the noisy power read the same way
-//              (predicted = linears * offset): every global access of the kernel is a full 16-B lane access on consecutive addresses.
-template <int NT>
-__global__ __launch_bounds__(256, 2) void head_kernel(const float* __restrict__ feats, const float* __restrict__ W,
-                                                      const float* __restrict__ bias, const float* __restrict__ linears,
-                                                      const float* __restrict__ stats, int rows, int F, int D, int N, int act,
-                                                      float* __restrict__ predicted, float* __restrict__ offset, int vec_io) {
-  constexpr int kStage = (kHM + NT * 32) * kHP;                     // floats: feature tile + weight chunk
-  constexpr int kEpi = 4 * kHHalf * (NT * 32);                       // floats: per wave 16 rows x (up to NT * 32) outputs
-  __shared__ __attribute__((aligned(16))) float smem[kStage > kEpi ? kStage : kEpi];
-  float* As = smem;
-  float* Ws = smem + kHM * kHP;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.x * kHM;
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  for (int k0 = 0; k0 < D; k0 += kHK) {
-    __syncthreads();
-    // ---- stage the normalised feature tile: item = (row, 16-B piece); 10 pieces per row
-    for (int it = tid; it < kHM * (kHK / 4); it += 256) {
-      const int r = it / (kHK / 4), c = it - r * (kHK / 4);
-      const int row = row0 + r, k = k0 + 4 * c;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < rows && k < D) {
-        const float* src = feats + (size_t)row * D + k;
-        if (k + 3 < D) {
-          v = *reinterpret_cast<const float4*>(src);
-        } else {
-          v.x = src[0];
-          if (k + 1 < D) v.y = src[1];
-          if (k + 2 < D) v.z = src[2];
-        }
-        if (stats) {
-          const float* sp = stats + ((size_t)(row / F) * D + k) * 2;           // (mean, 1 / (std + eps)) pairs
-          if (k + 3 < D) {
-            const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
-            v = make_float4((v.x - s0.x) * s0.y, (v.y - s0.z) * s0.w, (v.z - s1.x) * s1.y, (v.w - s1.z) * s1.w);
-          } else {
-            v.x = (v.x - sp[0]) * sp[1];
-            if (k + 1 < D) v.y = (v.y - sp[2]) * sp[3];
-            if (k + 2 < D) v.z = (v.z - sp[4]) * sp[5];
-          }
-        }
-      }
-      float* d = As + r * kHP + 4 * c;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    // ---- stage the weight chunk: item = (output n, 16-B piece)
-    for (int it = tid; it < NT * 32 * (kHK / 4); it += 256) {
-      const int n = it / (kHK / 4), c = it - n * (kHK / 4);
-      const int k = k0 + 4 * c;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n < N && k < D) {
-        const float* src = W + (size_t)n * D + k;
-        if (k + 3 < D) {
-          v = *reinterpret_cast<const float4*>(src);
-        } else {
-          v.x = src[0];
-          if (k + 1 < D) v.y = src[1];
-          if (k + 2 < D) v.z = src[2];
-        }
-      }
-      float* d = Ws + n * kHP + 4 * c;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    __syncthreads();
-    const float* ap = As + (wave * 32 + (lane & 31)) * kHP + (lane >> 5);
-    const float* wp = Ws + (lane & 31) * kHP + (lane >> 5);
-#pragma unroll 4
-    for (int kk = 0; kk < kHK; kk += 2) {
-      const float a = ap[kk];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wp[t * 32 * kHP + kk], acc[t], 0, 0, 0);
-    }
-  }
-
-  // ---- epilogue.  C/D map of 32x32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5): registers 8 h .. 8 h + 7 hold rows 16 h .. 16 h + 15
-  __syncthreads();                                              // every wave is done with the staging tiles
-  float* Es = smem + wave * (kHHalf * NT * 32);                 // this wave's [16][N] slab, rows packed at pitch N: the global layout of the span
-  float bn[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int n = t * 32 + (lane & 31);
-    bn[t] = (bias && n < N) ? bias[n] : 0.f;
-  }
-#pragma unroll
-  for (int h = 0; h < 32 / kHHalf; ++h) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int n = t * 32 + (lane & 31);
-      if (n < N) {
-#pragma unroll
-        for (int r8 = 0; r8 < kHHalf / 2; ++r8) {
-          const int r = (kHHalf / 2) * h + r8;
-          const int rl = (r & 3) + (kHHalf == 16 ? 8 * ((r >> 2) & 1) : 0) + 4 * (lane >> 5);       // row within the pass's 16 (8) rows
-          Es[rl * N + n] = apply_act(acc[t][r] + bn[t], act);
-        }
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const int rbase = row0 + wave * 32 + kHHalf * h;                            // a multiple of 16: the span starts 64-B aligned for any N
-    const int nrow = min(kHHalf, rows - rbase);
-    if (nrow > 0) {
-      const int cnt = nrow * N;
-      const size_t g = (size_t)rbase * N;
-      if (vec_io) {
-        const int nvec = cnt >> 2;
-        for (int i = lane; i < nvec; i += 64) {
-          const float4 o = *reinterpret_cast<const float4*>(Es + 4 * i);
-          if (offset) *reinterpret_cast<float4*>(offset + g + 4 * i) = o;
-          if (predicted) {
-            float4 p = o;
-            if (linears) {
-              const float4 l = *reinterpret_cast<const float4*>(linears + g + 4 * i);
-              p = make_float4(o.x * l.x, o.y * l.y, o.z * l.z, o.w * l.w);
-            }
-            *reinterpret_cast<float4*>(predicted + g + 4 * i) = p;
-          }
-        }
-        for (int i = 4 * nvec + lane; i < cnt; i += 64) {
-          const float o = Es[i];
-          if (offset) offset[g + i] = o;
-          if (predicted) predicted[g + i] = linears ? linears[g + i] * o : o;
-        }
-      } else {
-        for (int i = lane; i < cnt; i += 64) {
-          const float o = Es[i];
-          if (offset) offset[g + i] = o;
-          if (predicted) predicted[g + i] = linears ? linears[g + i] * o : o;
-        }
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-}
-
+constexpr int kHHalf = SE_HEAD_HALF;
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
-// Round 4: the SAME fp32 result on the bf16 matrix instruction.  VERDICT r3 #6: the kernel above is not HBM-bound but fp32-MFMA-bound --
-// v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate: at D = 201, 256 utterances, 23 GFLOP / 155 TF/s = 149 us against a 77 us HBM floor.
+// Round 4: the fp32 result on the bf16 matrix instruction.  VERDICT r3 #6: the round-3 kernel (v_mfma_f32_32x32x2_f32, retired: DESIGN
+// "retired kernels") was not HBM-bound but fp32-MFMA-bound -- that instruction runs at 1/16 of the bf16 rate: at D = 201, 256 utterances,
+// 23 GFLOP / 155 TF/s = 149 us against a 77 us HBM floor.
 // Here both operands are split into THREE bf16 terms, x = x1 + x2 + x3 (x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2): the residuals are
 // exact in fp32, the dropped remainder is <= 2^-24 |x|), and the product is the six terms whose weight is >= 2^-16:
 //     x w  =  x1 w1 + (x1 w2 + x2 w1) + (x2 w2 + x1 w3 + x3 w1)  + O(2^-24)
@@ -243,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const float* __restrict__ 
 // v_mfma_f32_32x32x16_bf16 (6 x 32 cycles for 16 k) replace eight v_mfma_f32_32x32x2_f32 (8 x 64 cycles): 2.7 x less matrix time, which puts the
 // kernel under its HBM floor.  Weights arrive pre-split (head_split_w_kernel: 3 planes [NT * 32][Kp] bf16, zero padded), the features are split
 // while they are staged (CMVN first, in fp32).  LDS: 16-k chunks, rows at a 48-B pitch (conflict-free ds_read_b128 of 16 consecutive rows):
-// 3 x (128 + NT * 32) x 48 B = 50.7 KB at N = 201 -> 3 workgroups per CU as before.  Epilogue: the kernel above's, unchanged (same C / D map).
+// 3 x (128 + NT * 32) x 48 B = 50.7 KB at N = 201 -> 3 workgroups per CU as before.  Epilogue: the round-3 kernel's (same C / D map).
 constexpr int kH3K = 16;          // k per chunk
 // developer ablation of head3_kernel (timing only, results wrong): -DSE_HEAD_ABL=<mask>: 1 no K loop, 2 no epilogue loads / stores (LDS round trip kept),
 // 4 no feature / statistics loads, 8 no MFMAs, 16 no activation
@@ -423,9 +271,10 @@ __global__ __launch_bounds__(256, 2) void head3_kernel(const float* __restrict__
 #undef SEH_DMA_W
 #undef SEH_LOAD_F
 
-  // ---- epilogue: as head_kernel (same accumulator map).  The slab is private to the wave and an LDS queue serves one wave's instructions in order: what
+  // ---- epilogue.  C/D map of 32x32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5): registers 8 h .. 8 h + 7 hold rows 16 h .. 16 h + 15.
+  //      The slab is private to the wave and an LDS queue serves one wave's instructions in order: what
   //      the exchange between its lanes needs is the LDS counter drained and the compiler kept from moving LDS accesses across the point.  A
-  //      workgroup-scope fence (the round-3 form, still in head_kernel) also waits for vmcnt(0): every pass then sat out the acknowledgement of its
+  //      workgroup-scope fence (the round-3 form) also waits for vmcnt(0): every pass then sat out the acknowledgement of its
   //      own 16-B stores AND the arrival of the next pass's noisy-power rows it had just requested -- the prefetch hid nothing
 #define SEH_LDS_WAVE_SYNC()                                   \
   do {                                                        \
@@ -841,16 +690,19 @@ static int launch_head3(const float* feats, const uint16_t* W3, int Kp, const fl
   return SE_OK;
 }
 
-template <int NT>
-static int launch_head(const float* feats, const float* W, const float* bias, const float* linears, const float* stats,
-                       int rows, int F, int D, int N, int act, float* predicted, float* offset, hipStream_t st) {
-  const int vec_io = ((((uintptr_t)predicted | (uintptr_t)offset | (uintptr_t)linears) % 16) == 0) ? 1 : 0;
-  // algorithmic bytes: features + noisy power in, predicted + offset out
-  se::ProfScope prof(se::kProfHead, 4.0 * rows * ((double)D + (linears ? N : 0) + (predicted ? N : 0) + (offset ? N : 0)), st);
-  hipLaunchKernelGGL((se::head_kernel<NT>), dim3((rows + se::kHM - 1) / se::kHM), dim3(256), 0, st, feats, W, bias, linears,
-                     stats, rows, F, D, N, act, predicted, offset, vec_io);
-  SE_LAUNCH_CHECK();
-  return SE_OK;
+// NT = ceil(N / 32) column tiles (N <= 256: checked by the callers)
+static int launch_head3_for(const float* feats, const uint16_t* W3, int Kp, const float* bias, const float* linears, const float* stats,
+                            int rows, int F, int D, int N, int act, float* predicted, float* offset, hipStream_t st) {
+  switch ((N + 31) / 32) {
+    case 1: return launch_head3<1>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 2: return launch_head3<2>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 3: return launch_head3<3>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 4: return launch_head3<4>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 5: return launch_head3<5>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 6: return launch_head3<6>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    case 7: return launch_head3<7>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+    default: return launch_head3<8>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
+  }
 }
 
 extern "C" int se_head_linear_f32(const float* feats, const float* W, const float* bias, const float* linears,
@@ -867,34 +719,11 @@ extern "C" int se_head_linear_f32(const float* feats, const float* W, const floa
     if (rc) return rc;
   }
   const int rows = B * F;
-  const int nt = (N + 31) / 32;
-  static const bool fp32_mfma = getenv("SE_AMD_HEAD_F32MFMA") != nullptr;      // developer A/B: the round-3 kernel on v_mfma_f32_32x32x2_f32
-  if (!fp32_mfma) {
-    const int rows_p = nt * 32, Kp = (D + 15) / 16 * 16;
-    uint16_t* W3 = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + (((size_t)B * D * 2 * sizeof(float) + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(se::head_split_w_kernel, dim3((rows_p * Kp + 255) / 256), dim3(256), 0, st, W, N, D, rows_p, Kp, W3);
-    SE_LAUNCH_CHECK();
-    switch (nt) {
-      case 1: return launch_head3<1>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 2: return launch_head3<2>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 3: return launch_head3<3>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 4: return launch_head3<4>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 5: return launch_head3<5>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 6: return launch_head3<6>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      case 7: return launch_head3<7>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-      default: return launch_head3<8>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    }
-  }
-  switch (nt) {
-    case 1: return launch_head<1>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 2: return launch_head<2>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 3: return launch_head<3>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 4: return launch_head<4>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 5: return launch_head<5>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 6: return launch_head<6>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 7: return launch_head<7>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    default: return launch_head<8>(feats, W, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-  }
+  const int rows_p = (N + 31) / 32 * 32, Kp = (D + 15) / 16 * 16;
+  uint16_t* W3 = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + (((size_t)B * D * 2 * sizeof(float) + 255) & ~(size_t)255));
+  hipLaunchKernelGGL(se::head_split_w_kernel, dim3((rows_p * Kp + 255) / 256), dim3(256), 0, st, W, N, D, rows_p, Kp, W3);
+  SE_LAUNCH_CHECK();
+  return launch_head3_for(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
 }
 
 
@@ -946,19 +775,10 @@ extern "C" int se_head_linear_pre_f32(const float* feats, const uint16_t* W3, co
   SE_REQUIRE(feats && W3 && (predicted || offset), "se_head_linear_pre_f32: null argument");
   SE_REQUIRE(B > 0 && B <= 65535 && F >= 2 && D > 0 && N > 0 && N <= 256, "se_head_linear_pre_f32: bad shape B=%d F=%d D=%d N=%d (N <= 256)", B, F, D, N);
   hipStream_t st = se::as_stream(stream);
-  const int rows = B * F, nt = (N + 31) / 32, Kp = (D + 15) / 16 * 16;
+  const int rows = B * F, Kp = (D + 15) / 16 * 16;
   if (head5_ok(linears, predicted, offset, nullptr, F, D, N, act))
     return launch_head5(feats, W3, bias, linears, stats, rows, F, D, N, act, predicted, offset, nullptr, nullptr, 0, nullptr, st);
-  switch (nt) {
-    case 1: return launch_head3<1>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 2: return launch_head3<2>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 3: return launch_head3<3>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 4: return launch_head3<4>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 5: return launch_head3<5>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 6: return launch_head3<6>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    case 7: return launch_head3<7>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-    default: return launch_head3<8>(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
-  }
+  return launch_head3_for(feats, W3, Kp, bias, linears, stats, rows, F, D, N, act, predicted, offset, st);
 }
 
 // The evaluate()-style pass of a mask head scored by objective.SISDR (runner.py:556-575 with vcb.yaml / pseudo_noise.yaml): se_head_linear_pre_f32 AND

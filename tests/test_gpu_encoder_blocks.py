@@ -100,6 +100,66 @@ def test_gemm_n768_row_complete_plain(gpu, M, K):
     assert torch.equal(o32, Wi.T[torch.arange(M, device=gpu) % K])
 
 
+GEMM_ROUTES = ('Tile128x2', 'RowComplete768', 'Persistent256', 'Tile256', 'PingPong256x128', 'Lockstep256x128')      # csrc/gemm_route.h
+
+
+@pytest.mark.parametrize('M,N,K,residual,out,route', [
+    (4100, 768, 1536, False, 'f32', 'Tile256'),                 # 33 row tiles: below the row-complete kernel's 160
+    (4100, 768, 1536, True, 'bf16', 'PingPong256x128'),         # residual -> bf16: no 256 x 256 instantiation
+    (4100, 1536, 128, False, 'both', 'PingPong256x128'),        # two outputs: the generic epilogue
+    (7169, 2304, 256, False, 'bf16', 'Persistent256'),          # 29 x 9 = 261 tiles, ragged last row tile
+    (7168, 2304, 256, False, 'bf16', 'Tile256'),                # 28 x 9 = 252 tiles: one workgroup per tile
+    (4100, 768, 64, False, 'f32', 'Lockstep256x128'),           # one K-tile
+    (4100, 201, 128, False, 'f32', 'PingPong256x128'),          # ragged N: the generic epilogue's scalar tail
+])
+def test_gemm_large_m_routes_vs_torch(gpu, M, N, K, residual, out, route):
+    """se_gemm_bf16 past the small-batch threshold (test_gemm_vs_torch stays below it): one case per kernel the dispatch reaches there, at the
+    smallest shape that does; M = 4100 and 7169 leave ragged last row tiles.  The route is asserted first (se_gemm_route_of), then the result
+    against fp64 on the same bf16 operands with test_gemm_vs_torch's bounds, then an exact-integer case that catches layout slips."""
+    import ctypes
+    L = _lib()
+    fn = L.load().se_gemm_route_of
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 12
+    got = fn(M, N, K, K, K, N, 0, 1, int(residual), int(out in ('bf16', 'both')), int(out in ('f32', 'both')), 1)
+    assert GEMM_ROUTES[got] == route
+
+    def check_aligned(*ts):
+        assert all(t is None or t.data_ptr() % 16 == 0 for t in ts)      # what the asserted route assumed
+
+    torch.manual_seed(M + N + K)
+    A = torch.randn(M, K, device=gpu).bfloat16()
+    W = (torch.randn(N, K, device=gpu) * 0.05).bfloat16()
+    bias = torch.randn(N, device=gpu)
+    res = torch.randn(M, N, device=gpu) if residual else None
+    check_aligned(A, W, bias, res)
+    ref = A.float().double() @ W.float().double().T + bias.double() + (res.double() if residual else 0.0)
+    o32, o16 = gemm(A, W, bias, res, 0, out)
+    check_aligned(o32, o16)
+    scale = ref.abs().max().item()
+    if o32 is not None:
+        err = (o32.double() - ref).abs().max().item()
+        print(f'fp32 err {err:.3e} bound {2e-5 * scale + 1e-5 * math.sqrt(K):.3e}')
+        assert err < 2e-5 * scale + 1e-5 * math.sqrt(K)
+    if o16 is not None:
+        err = (o16.double() - ref).abs().max().item()
+        print(f'bf16 err {err:.3e} bound {8e-3 * scale:.3e}')
+        assert err < 8e-3 * scale
+    # exact: A rows are unit vectors (row m selects column m % K of W^T), W / bias / residual small integers (sums below 2^8: exact in bf16)
+    rows = torch.arange(M, device=gpu)
+    Ai = torch.zeros(M, K, device=gpu)
+    Ai[rows, rows % K] = 1.0
+    Wi = ((torch.arange(N * K, device=gpu).reshape(N, K) * 7) % 61 - 30).float()
+    bi = (torch.arange(N, device=gpu) % 9 - 4).float()
+    ri = ((rows[:, None] * 3 + torch.arange(N, device=gpu)[None, :]) % 17 - 8).float() if residual else None
+    want = Wi.T[rows % K] + bi + (ri if residual else 0.0)
+    o32, o16 = gemm(Ai.bfloat16(), Wi.bfloat16(), bi, ri, 0, out)
+    if o32 is not None:
+        assert torch.equal(o32, want)
+    if o16 is not None:
+        assert torch.equal(o16.float(), want)
+
+
 def mhsa_ref(qkv, lengths, B, T, heads):
     H = heads * 64
     x = qkv.float().view(B, T, 3, heads, 64).permute(2, 0, 3, 1, 4).double()    # (3, B, h, T, 64)

@@ -78,7 +78,7 @@ def bench_gemm_qkv():
     def run():
         L.check(lib.se_gemm_bf16(L.ptr(A), K, L.ptr(W), K, L.ptr(bias), None, M, N, K, 0, L.ptr(o16), None, N, L.stream()), 'gemm')
     ms = timeit(run)
-    print(f'gemm QKV M={M} N={N} K={K} [SE_AMD_GEMM3_SCHED={os.environ.get("SE_AMD_GEMM3_SCHED")}]: {ms*1e3:8.1f} us  {2.0*M*N*K/ms/1e9:8.1f} TF/s', flush=True)
+    print(f'gemm QKV M={M} N={N} K={K}: {ms*1e3:8.1f} us  {2.0*M*N*K/ms/1e9:8.1f} TF/s', flush=True)
 
 
 def bench_gemm_ksweep():
