@@ -54,8 +54,17 @@ int se_device_available(void);
  * Preprocessor plan: STFT geometry + device tables (Hann window, twiddles, sparse HTK mel bank).
  * Replaces OnlinePreprocessor.__init__ (S3PRL utility/preprocessor.py; constructed at
  * run_downstream.py:159 from config/pretrain_sample.yaml:39-48).
- * The kernels are specialised for n_fft = 400 (n_freq = 201), hop = 160, win <= 400; anything else
- * returns SE_ERR_UNSUPPORTED.
+ * Two kinds of plan behind one handle; every entry point that takes a plan dispatches on the kind:
+ *   se_plan_create      the specialised fast path: n_fft = 400 (n_freq = 201), hop = 160, win <= 400; anything else returns
+ *                       SE_ERR_UNSUPPORTED.
+ *   se_plan_create_any  the general path (run-time-scheduled mixed-radix FFT), for every geometry of the SUPPORTED SET:
+ *                         n_fft = 2 (n_freq - 1) = 2 m with m = 2^a 3^b 5^c and 16 <= m <= 512  (n_fft 32 ... 1024)
+ *                         2 <= win <= n_fft       (periodic Hann of length win, centred in n_fft: left pad (n_fft - win) / 2, as torch.stft)
+ *                         ceil(n_fft / 8) <= hop <= win / 2   (bounded overlap; the overlap-add envelope cannot vanish)
+ *                         1 <= n_mels <= 128      (triangles of any width)
+ *                       and calls need T > n_fft / 2.  Anything else returns SE_ERR_UNSUPPORTED with a message naming the violated rule.
+ *                       400 / 160 / 201 is in the set: the two kernel families can be compared on it.
+ * Output layouts, the encoded-phase word, zero fill and the square-sum accumulators are the same for both kinds.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct se_plan se_plan;
 
@@ -68,8 +77,14 @@ typedef struct se_geometry {
 } se_geometry;
 
 int se_plan_create(const se_geometry* geom, se_plan** out);
+int se_plan_create_any(const se_geometry* geom, se_plan** out);
 void se_plan_destroy(se_plan* plan);
-/* copies the plan's host-side tables out (for tests): window[n_fft = 400] (win centred), mel_fb[n_freq*n_mels] row-major (k, m). */
+/* n_fft of the plan (400 for a plan of se_plan_create); -1 for NULL. */
+int se_plan_n_fft(const se_plan* plan);
+/* Work partition of a general plan's kernels: frames per workgroup of the forward transform (inverse == 0) or hop-blocks of output per
+ * workgroup of the inverse transform (inverse != 0); 0 for a plan of se_plan_create.  For tests that want to straddle workgroup borders. */
+int se_plan_chunk_frames(const se_plan* plan, int inverse);
+/* copies the plan's host-side tables out (for tests): window[n_fft] (win centred; n_fft = se_plan_n_fft), mel_fb[n_freq*n_mels] row-major (k, m). */
 int se_plan_tables(const se_plan* plan, float* window, float* mel_fb);
 
 /* Number of STFT frames of a T-sample signal: T / hop + 1 (runner.py:455). */
@@ -138,7 +153,7 @@ int se_features3_f32(const float* raw, int raw_time_major, int B, int D, int F, 
 
 /*
  * se_istft_f32 -- row A6: OnlinePreprocessor.istft(linears, phases) (runner.py:267): mag = power^(1/linear_power),
- * (mag cos phi, mag sin phi) -> inverse 400-pt real DFT -> x Hann -> overlap-add -> / sum(w^2) -> trim n_fft/2.
+ * (mag cos phi, mag sin phi) -> inverse n_fft-point real DFT -> x Hann -> overlap-add -> / sum(w^2) -> trim n_fft/2.
  *   power, phase (B, F, K) time-major;   wav_out (B, wav_stride) with the first hop*(F-1) samples written and
  *   samples [hop*(F-1), wav_stride) zero-filled (the right-pad of runner.py:268).
  *   sumsq_out (B) optional: sum over n < lengths[b] of wav^2 (feeds se_dbnorm_f32); zeroed inside this call

@@ -57,7 +57,10 @@ SIGNATURES = {
     'se_version': (c_char_p, []),
     'se_device_available': (c_int, []),
     'se_plan_create': (c_int, [POINTER(Geometry), POINTER(_P)]),
+    'se_plan_create_any': (c_int, [POINTER(Geometry), POINTER(_P)]),
     'se_plan_destroy': (None, [_P]),
+    'se_plan_n_fft': (c_int, [_P]),
+    'se_plan_chunk_frames': (c_int, [_P, c_int]),
     'se_plan_tables': (c_int, [_P, _P, _P]),
     'se_num_frames': (c_int, [_P, c_int]),
     'se_stft_f32': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),

@@ -297,10 +297,12 @@ extern "C" int se_istft_f32(const se_plan* plan, const float* power, const float
                             const int64_t* lengths, float* sumsq_out, void* stream) {
   SE_REQUIRE(plan && power && phase && wav_out, "se_istft_f32: null argument");
   SE_REQUIRE(B > 0 && B <= 65535 && F >= 2, "se_istft_f32: bad B=%d F=%d", B, F);
-  const int n_out = se::kHop * (F - 1);
+  const int n_out = plan->geom.hop * (F - 1);
   SE_REQUIRE(wav_stride >= n_out, "se_istft_f32: wav_stride=%d < %d output samples", wav_stride, n_out);
   SE_REQUIRE(linear_power > 0.f, "se_istft_f32: linear_power must be positive");
   SE_REQUIRE(sumsq_out == nullptr || lengths != nullptr, "se_istft_f32: sumsq_out needs lengths");
+  if (plan->general)      // a plan of se_plan_create_any: the general kernel (istftg.hip)
+    return se_istftg_launch(plan, power, phase, 0, 0, linear_power, B, F, wav_out, wav_stride, lengths, sumsq_out, nullptr, 0, nullptr, stream);
   hipStream_t st = se::as_stream(stream);
   if (sumsq_out) { const int zrc_ = se::zero_async(sumsq_out, sizeof(float) * B, st); if (zrc_) return zrc_; }
   dim3 grid((n_out + se::kISpan - 1) / se::kISpan, B);
@@ -325,10 +327,13 @@ extern "C" int se_istft_tphase_f32(const se_plan* plan, const float* power, cons
                                    const float* ref, int ref_stride, float* ref_sumsq_out, void* stream) {
   SE_REQUIRE(plan && power && tphase && wav_out, "se_istft_tphase_f32: null argument");
   SE_REQUIRE(B > 0 && B <= 65535 && F >= 2, "se_istft_tphase_f32: bad B=%d F=%d", B, F);
-  const int n_out = se::kHop * (F - 1);
+  const int n_out = plan->geom.hop * (F - 1);
   SE_REQUIRE(wav_stride >= n_out, "se_istft_tphase_f32: wav_stride=%d < %d output samples", wav_stride, n_out);
   SE_REQUIRE(sumsq_out == nullptr || lengths != nullptr, "se_istft_tphase_f32: sumsq_out needs lengths");
   SE_REQUIRE(ref_sumsq_out == nullptr || (ref && sumsq_out && ref_stride >= n_out), "se_istft_tphase_f32: ref_sumsq_out needs ref (row stride >= %d) and sumsq_out", n_out);
+  if (plan->general)
+    return se_istftg_launch(plan, power, reinterpret_cast<const float*>(tphase), 1, log_input, 2.0f, B, F, wav_out, wav_stride, lengths, sumsq_out, ref,
+                            ref_stride, ref_sumsq_out, stream);
 #ifdef SE_AMD_EXPERIMENTS
   static const bool use2 = getenv("SE_AMD_STFT2") != nullptr;
 #else

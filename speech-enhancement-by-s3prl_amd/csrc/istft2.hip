@@ -228,6 +228,10 @@ static int pick_hop_blocks(int n_blocks, long long B, int slots) {
 extern "C" int se_istft2p_tphase_f32(const se_plan* plan, const float* power, const unsigned* tphase, int B, int F, int log_input,
                                    float* wav_out, int wav_stride, const int64_t* lengths, float* sumsq_out, void* stream) {
   SE_REQUIRE(plan && power && tphase && wav_out, "se_istft2p_tphase_f32: null argument");
+  if (plan->general) {
+    se::set_error("se_istft2p_tphase_f32: the persistent 400-point kernel cannot serve a general plan");
+    return SE_ERR_UNSUPPORTED;
+  }
   SE_REQUIRE(B > 0 && F >= 2, "se_istft2p_tphase_f32: bad B=%d F=%d", B, F);
   const int n_out = se::kHop * (F - 1);
   SE_REQUIRE(wav_stride >= n_out, "se_istft2p_tphase_f32: wav_stride=%d < %d output samples", wav_stride, n_out);

@@ -155,6 +155,112 @@ extern "C" int se_plan_create(const se_geometry* geom, se_plan** out) {
   return SE_OK;
 }
 
+// The general plan: any geometry of the supported set (include/se_amd.h), served by stftg.hip / istftg.hip.  All tables in float64 on the host.
+extern "C" int se_plan_create_any(const se_geometry* geom, se_plan** out) {
+  SE_REQUIRE(geom && out, "se_plan_create_any: null argument");
+  char why[256];
+  if (se::fftg_check_geometry(geom->win, geom->hop, geom->n_freq, geom->n_mels, why, sizeof(why)) != 0) {
+    se::set_error("se_plan_create_any: unsupported geometry (n_freq=%d hop=%d win=%d n_mels=%d): %s", geom->n_freq, geom->hop, geom->win,
+                  geom->n_mels, why);
+    return SE_ERR_UNSUPPORTED;
+  }
+  se_plan* p = new se_plan();
+  p->geom = *geom;
+  p->d_blob = nullptr;
+  p->general = true;
+  p->m = geom->n_freq - 1;
+  p->n_fft = 2 * p->m;
+  const int m = p->m, n_fft = p->n_fft, M = geom->n_mels;
+  if (!se::fftg_make_schedule(m, &p->sched)) {
+    delete p;
+    se::set_error("se_plan_create_any: no radix schedule for m=%d", m);
+    return SE_ERR_UNSUPPORTED;
+  }
+  p->h_window.resize(n_fft);
+  se::fftg_make_window(n_fft, geom->win, p->h_window.data());
+  build_mel(*geom, p->h_melfb);
+  std::vector<float> winv(n_fft), wsq(n_fft);
+  for (int n = 0; n < n_fft; ++n) {
+    winv[n] = (float)((double)p->h_window[n] / (double)m);
+    wsq[n] = p->h_window[n] * p->h_window[n];
+  }
+  std::vector<se::cf> tw(m), rtw(m);
+  se::fftg_make_twiddles(m, tw.data(), rtw.data());
+  // CSR mel bank: per filter the span [first, last] of its non-zero bins, any width
+  std::vector<int> csr(2 * M + 1, 0);
+  for (int f = 0; f < M; ++f) {
+    int lo = -1, hi = -2;
+    for (int k = 0; k < geom->n_freq; ++k)
+      if (p->h_melfb[(size_t)k * M + f] != 0.f) {
+        if (lo < 0) lo = k;
+        hi = k;
+      }
+    csr[M + 1 + f] = lo < 0 ? 0 : lo;
+    for (int k = lo; k <= hi; ++k) {
+      int bits;
+      memcpy(&bits, &p->h_melfb[(size_t)k * M + f], 4);
+      csr.push_back(bits);
+    }
+    csr[f + 1] = (int)csr.size() - (2 * M + 1);
+  }
+  p->mel_words = (int)csr.size();
+  p->fwd = se::stftg_shape(m, p->mel_words);
+  p->inv = se::istftg_shape(m, geom->hop);
+  if (p->fwd.planeN > p->fwd.bufN || p->fwd.lds > se::kGInvLdsLarge || p->inv.HB < 1 || p->inv.lds > se::kGInvLdsLarge + 1024) {
+    delete p;
+    se::set_error("se_plan_create_any: no launch shape for m=%d hop=%d within the LDS", m, geom->hop);
+    return SE_ERR_UNSUPPORTED;
+  }
+
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    delete p;
+    se::set_error("se_plan_create_any: no HIP device visible (the product path has no CPU fallback)");
+    return SE_ERR_NO_DEVICE;
+  }
+  SE_HIP(hipGetDevice(&p->device));
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_win = 0, o_winv = o_win + al(4 * n_fft), o_wsq = o_winv + al(4 * n_fft), o_tw = o_wsq + al(4 * n_fft), o_rtw = o_tw + al(8 * m),
+               o_mel = o_rtw + al(8 * m), total = o_mel + al(4 * csr.size());
+  e = hipMalloc(&p->d_blob, total);
+  if (e != hipSuccess) {
+    delete p;
+    return se::hip_fail(e, "hipMalloc(plan tables)", __FILE__, __LINE__);
+  }
+  char* base = (char*)p->d_blob;
+  p->g_window = (float*)(base + o_win);
+  p->g_window_inv = (float*)(base + o_winv);
+  p->g_window_sq = (float*)(base + o_wsq);
+  p->g_tw = (se::cf*)(base + o_tw);
+  p->g_rtw = (se::cf*)(base + o_rtw);
+  p->g_mel = (int*)(base + o_mel);
+  struct { void* dst; const void* src; size_t bytes; } copies[] = {
+      {p->g_window, p->h_window.data(), (size_t)4 * n_fft}, {p->g_window_inv, winv.data(), (size_t)4 * n_fft}, {p->g_window_sq, wsq.data(), (size_t)4 * n_fft},
+      {p->g_tw, tw.data(), (size_t)8 * m}, {p->g_rtw, rtw.data(), (size_t)8 * m}, {p->g_mel, csr.data(), 4 * csr.size()}};
+  for (auto& c : copies) {
+    e = hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      se_plan_destroy(p);
+      return se::hip_fail(e, "hipMemcpy(plan tables)", __FILE__, __LINE__);
+    }
+  }
+  *out = p;
+  return SE_OK;
+}
+
+extern "C" int se_plan_n_fft(const se_plan* plan) {
+  if (!plan) return -1;
+  return plan->general ? plan->n_fft : se::kNfft;
+}
+
+extern "C" int se_plan_chunk_frames(const se_plan* plan, int inverse) {
+  if (!plan) return -1;
+  if (!plan->general) return 0;
+  return inverse ? plan->inv.HB : plan->fwd.FR;
+}
+
 extern "C" void se_plan_destroy(se_plan* plan) {
   if (!plan) return;
   if (plan->d_blob) (void)hipFree(plan->d_blob);
@@ -163,7 +269,7 @@ extern "C" void se_plan_destroy(se_plan* plan) {
 
 extern "C" int se_plan_tables(const se_plan* plan, float* window, float* mel_fb) {
   SE_REQUIRE(plan, "se_plan_tables: null plan");
-  if (window) memcpy(window, plan->h_window.data(), sizeof(float) * se::kNfft);
+  if (window) memcpy(window, plan->h_window.data(), sizeof(float) * plan->h_window.size());
   if (mel_fb) memcpy(mel_fb, plan->h_melfb.data(), sizeof(float) * plan->h_melfb.size());
   return SE_OK;
 }

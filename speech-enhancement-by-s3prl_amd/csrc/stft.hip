@@ -389,6 +389,10 @@ extern "C" int se_stft_f32(const se_plan* plan, const float* wavs, int B, int C,
                            float* power, float* phase, float* complx, float* mel, void* stream) {
   SE_REQUIRE(plan && wavs, "se_stft_f32: null plan / wavs");
   SE_REQUIRE(B > 0 && C > 0 && channel >= 0 && channel < C, "se_stft_f32: bad B=%d C=%d channel=%d", B, C, channel);
+  if (plan->general) {      // a plan of se_plan_create_any: the general kernel (stftg.hip)
+    const se_stftg_job gjob{power, phase, complx, mel, channel, (((uintptr_t)power | (uintptr_t)phase) % 16) == 0, 0};
+    return se_stftg_launch(plan, wavs, B, C, T, &gjob, 1, stream);
+  }
   SE_REQUIRE(T > se::kHalf, "se_stft_f32: T=%d must exceed n_fft/2=%d (reflect padding)", T, se::kHalf);
   SE_REQUIRE(B <= 65535, "se_stft_f32: B=%d exceeds grid.y limit", B);
   unsigned long long* dbgbuf = nullptr;
@@ -404,6 +408,11 @@ extern "C" int se_stft2_f32(const se_plan* plan, const float* wavs, int B, int C
                             float* mel_a, int channel_b, float* power_b, float* phase_b, float* complx_b, float* mel_b, void* stream) {
   SE_REQUIRE(plan && wavs, "se_stft2_f32: null plan / wavs");
   SE_REQUIRE(B > 0 && C > 0 && channel_a >= 0 && channel_a < C && channel_b >= 0 && channel_b < C, "se_stft2_f32: bad B=%d C=%d channels=%d,%d", B, C, channel_a, channel_b);
+  if (plan->general) {
+    const se_stftg_job gjobs[2] = {{power_a, phase_a, complx_a, mel_a, channel_a, (((uintptr_t)power_a | (uintptr_t)phase_a) % 16) == 0, 0},
+                                   {power_b, phase_b, complx_b, mel_b, channel_b, (((uintptr_t)power_b | (uintptr_t)phase_b) % 16) == 0, 0}};
+    return se_stftg_launch(plan, wavs, B, C, T, gjobs, 2, stream);
+  }
   SE_REQUIRE(T > se::kHalf, "se_stft2_f32: T=%d must exceed n_fft/2=%d (reflect padding)", T, se::kHalf);
   SE_REQUIRE(B <= 65535, "se_stft2_f32: B=%d exceeds grid.y limit", B);
   const se::StftOut jobs[2] = {{power_a, phase_a, complx_a, mel_a, channel_a, (((uintptr_t)power_a | (uintptr_t)phase_a) % 16) == 0, 0},
@@ -422,6 +431,13 @@ extern "C" int se_stft_tphase_f32(const se_plan* plan, const float* wavs, int B,
   SE_REQUIRE(plan && wavs, "se_stft_tphase_f32: null plan / wavs");
   const int njobs = channel_b >= 0 ? 2 : 1;
   SE_REQUIRE(B > 0 && C > 0 && channel_a >= 0 && channel_a < C && channel_b < C, "se_stft_tphase_f32: bad B=%d C=%d channels=%d,%d", B, C, channel_a, channel_b);
+  if (plan->general) {
+    float* ga = reinterpret_cast<float*>(tphase_a);
+    float* gb = reinterpret_cast<float*>(tphase_b);
+    const se_stftg_job gjobs[2] = {{power_a, ga, nullptr, mel_a, channel_a, (((uintptr_t)power_a | (uintptr_t)ga) % 16) == 0, 1},
+                                   {power_b, gb, nullptr, mel_b, njobs > 1 ? channel_b : channel_a, (((uintptr_t)power_b | (uintptr_t)gb) % 16) == 0, 1}};
+    return se_stftg_launch(plan, wavs, B, C, T, gjobs, njobs, stream);
+  }
   SE_REQUIRE(T > se::kHalf, "se_stft_tphase_f32: T=%d must exceed n_fft/2=%d (reflect padding)", T, se::kHalf);
   SE_REQUIRE(B <= 65535, "se_stft_tphase_f32: B=%d exceeds grid.y limit", B);
 #ifdef SE_AMD_EXPERIMENTS

@@ -95,7 +95,7 @@ class OnlinePreprocessor(nn.Module):
         self.register_buffer('_window', torch.hann_window(win))
         self.feat_list = feat_list
         g = torch.Generator().manual_seed(0)
-        self.register_buffer('_pseudo_wavs', torch.randn(N_SAMPLED_PSEUDO_WAV, sample_rate, generator=g))
+        self.register_buffer('_pseudo_wavs', torch.randn(N_SAMPLED_PSEUDO_WAV, max(sample_rate, n_fft), generator=g))
         self.eps = eps
         self._plans = {}          # device index -> se_plan* (not pickled / deep-copied)
 
@@ -124,6 +124,8 @@ class OnlinePreprocessor(nn.Module):
         except Exception:
             pass
 
+    general_plan = False       # True: the general kernels also at 201 / 160 / win <= 400 (cross-checks and measurements of the two kernel families)
+
     def _plan(self, device, n_mels=None):
         idx = device.index if device.index is not None else torch.cuda.current_device()
         n_mels = self._n_mels if n_mels is None else n_mels
@@ -134,8 +136,12 @@ class OnlinePreprocessor(nn.Module):
             geom = _lib.Geometry(self._sample_rate, self._win_args['win_length'], self._win_args['hop_length'],
                                  self._n_freq, n_mels)
             out = _lib.c_void_p()
+            # the specialised 400-point kernels for the geometry they are built for, the general kernels for every other supported one
+            fixed = (self._n_freq == 201 and self._win_args['hop_length'] == 160 and 2 <= self._win_args['win_length'] <= 400 and
+                     not self.general_plan)
+            create, what = (lib.se_plan_create, 'se_plan_create') if fixed else (lib.se_plan_create_any, 'se_plan_create_any')
             with torch.cuda.device(idx):
-                _lib.check(lib.se_plan_create(geom, out), 'se_plan_create')
+                _lib.check(create(geom, out), what)
             plan = self._plans[key] = out.value
         return plan
 
