@@ -169,14 +169,17 @@ int se_istft_f32(const se_plan* plan, const float* power, const float* phase, in
  * X' = sqrt(power) * (+-(1 - t^2), 2 t) / (1 + t^2), then as se_istft_f32 (linear_power = 2).  log_input != 0: `power` holds log_predicted
  * of a log-target head (model.py:108-124, predicted = exp(log_predicted)).  Outputs, zero fill and sumsq_out as se_istft_f32.
  * ref / ref_stride / ref_sumsq_out (optional): the reference waveform of the level normalisation (runner.py:570 passes wav_tar): its masked
- * square sum over n < min(lengths[b], hop (F-1)) is accumulated by the same launch (what se_masked_sumsq_f32 computes on its own).
+ * square sum over n < min(lengths[b], wav_stride, ref_stride) -- the whole mask of utils.py:26-46, which runs past the hop (F-1) samples the
+ * inverse transform returns when T is no multiple of the hop -- comes out of the same call (what se_masked_sumsq_f32 computes on its own: the
+ * default kernel accumulates it in its own launch, the log_input form calls se_masked_sumsq_f32).
  */
 int se_istft_tphase_f32(const se_plan* plan, const float* power, const unsigned* tphase, int B, int F, int log_input,
                         float* wav_out, int wav_stride, const int64_t* lengths, float* sumsq_out,
                         const float* ref, int ref_stride, float* ref_sumsq_out, void* stream);
 
 /*
- * se_masked_sumsq_f32 -- utils.py:26-29 numerator: sums[b] = sum_{n < lengths[b]} x[b,n]^2  (sums zeroed inside).
+ * se_masked_sumsq_f32 -- utils.py:26-29 numerator: sums[b] = sum_{n < min(lengths[b], T)} x[b,n]^2  (sums zeroed inside); a negative length
+ * is an empty mask (sum 0), here and in se_dbnorm_f32.
  */
 int se_masked_sumsq_f32(const float* x, int B, int T, int x_stride, const int64_t* lengths, float* sums, void* stream);
 
@@ -257,6 +260,8 @@ int se_head_linear_dx_f32(const float* feats, const float* linears, const float*
  *   under data parallelism both are all-reduced first).  sums is a DEVICE double[2], zeroed inside.
  *   grad (optional, may be NULL): sign(log_pred - log(tar+eps)) on valid elements, 0 elsewhere -- the caller
  *   scales by 1/sums[1] (global count).
+ *   A negative length counts as 0, as in se_sisdr_spec_f32 / se_sisdr_spec_loss_f32: no valid frame (len_div == 0), or the one frame of an
+ *   empty waveform (len_div > 0: 0 / len_div + 1).
  */
 int se_l1_masked_f32(const float* log_pred, const float* linear_tar, const int64_t* frame_lengths,
                      int B, int F, int K, float eps, double* sums, float* grad, void* stream);

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void masked_sumsq_kernel(const float* __restri
                                                            const int64_t* __restrict__ lengths, float* __restrict__ sums) {
   __shared__ float red[4];
   const int b = blockIdx.y;
-  const int len = (int)min((int64_t)T, lengths[b]);
+  const int len = (int)min((int64_t)T, max((int64_t)0, lengths[b]));      // a negative length is an empty mask (its `len & 3` tail would read in front of the row)
   const float* row = x + (size_t)b * x_stride;
   float ss = 0.f;
   if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {          // 16-B loads, two per thread in flight
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void dbnorm_kernel(float* __restrict__ wav, in
                                                      const float* __restrict__ ref_sumsq, float fixed_db, float eps) {
   const int b = blockIdx.y;
   // masked_mean = sum / (count + eps)   (utils.py:28); count = min(len, T) ones in the length mask
-  const float cnt = (float)min((int64_t)T, lengths[b]);
+  const float cnt = (float)min((int64_t)T, max((int64_t)0, lengths[b]));
   const float denom = cnt + eps;
   const float target_db = ref_sumsq ? 10.0f * log10f(ref_sumsq[b] / denom) : fixed_db;
   const float scale = sqrtf(powf(10.0f, target_db / 10.0f) / (wav_sumsq[b] / denom + eps));

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ log_p
   __shared__ float red[4];
   const int b = blockIdx.y;
   // 32-bit arithmetic on purpose: a 64-bit division per thread is ~100 instructions (it made this launch 8 us slower than the form it replaces)
-  const int wl = (int)min(frame_lengths[b], (int64_t)0x7fffffff);
+  const int wl = (int)min(max(frame_lengths[b], (int64_t)0), (int64_t)0x7fffffff);      // a negative length counts as 0, as in objectives.hip: frames_of
   const int fl = len_div > 0 ? wl / len_div + 1 : wl;
   const int len = min(F, fl);
   const size_t base = (size_t)b * F * K;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ log_p
     double acc = 0.0, cnt = 0.0;
     for (int i = threadIdx.x; i < total; i += 256) acc += __hip_atomic_load(&slab[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int bb = threadIdx.x; bb < (int)gridDim.y; bb += 256) {
-      const int wl2 = (int)min(frame_lengths[bb], (int64_t)0x7fffffff);
+      const int wl2 = (int)min(max(frame_lengths[bb], (int64_t)0), (int64_t)0x7fffffff);
       cnt += (double)(min(F, len_div > 0 ? wl2 / len_div + 1 : wl2) * K);
     }
 #pragma unroll
