@@ -543,6 +543,27 @@ int se_mix_f32(const float* speech, int ld_s, const int64_t* len_s, const float*
 int se_sisdr_f32(const float* src, const float* tar, int ld, const int64_t* lengths, int B, float eps, double* sums, float* sisdr,
                  void* stream);
 
+/* evaluation.stoi_eval / estoi_eval (evaluation.py:28-36: pystoi.stoi(tar, src, sr, extended)) for each utterance over its first lengths[b]
+ * samples (runner.py:597-603), on the device.  The signal chain is restated here, not linked: parity unpinned vs pystoi.
+ *   resample   sample_rate -> 10000 by a rational polyphase FIR (16000: 5 / 8, 581 Kaiser-windowed taps, zero phase; 10000: skipped)
+ *   mask       frames of 256 at hop 128 of the CLEAN signal (window hanning(258)[1:-1]); a frame is kept iff its energy in dB exceeds the
+ *              loudest frame's - 40; the kept windowed frames of both signals are overlap-added in kept order
+ *   bands      512-point one-sided DFT of the compacted signals' frames, 15 third-octave bands from 150 Hz: sqrt of the summed |X|^2
+ *   score      segments of 30 frames; extended == 0: STOI (scaled + clipped, row-normalised correlation, mean over segments and bands),
+ *              extended != 0: ESTOI (row- then column-normalised, mean over segments and frames; no dither)
+ *   Fewer than 30 kept frames (short, empty, or a length <= 0) gives exactly 1e-5.
+ * se_stoi_plan_create: sample_rate 16000 or 10000, anything else returns SE_ERR_UNSUPPORTED with a message that says so (before a device is
+ * looked for).  clean, processed (B, ld) fp32, ld >= T; lengths (B) int64, clamped to [0, T], NULL: T for all.  stoi_out (B) fp32.  Optional
+ * outputs: kept_out (B) = kept frames per utterance; tob_out (2, B, 15, Fmax) = the envelopes of clean (0) and processed (1), Fmax = the frame
+ * count of T samples, columns past kept_out[b] zero.  workspace: se_stoi_workspace_bytes(plan, B, T) bytes, no clearing needed.  All launches
+ * are asynchronous on `stream`; fixed summation order. */
+typedef struct se_stoi_plan se_stoi_plan;
+int se_stoi_plan_create(int sample_rate, se_stoi_plan** out);
+void se_stoi_plan_destroy(se_stoi_plan* plan);
+size_t se_stoi_workspace_bytes(const se_stoi_plan* plan, int B, int T);
+int se_stoi_f32(const se_stoi_plan* plan, const float* clean, const float* processed, int ld, const int64_t* lengths, int B, int T, int extended,
+                float* stoi_out, int32_t* kept_out, float* tob_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Recurrent core of the (Bi)LSTM downstream heads (model.py:37-91, nn.LSTM hidden 256).
  * The input projection and all gradient GEMMs run on se_gemm_bf16 / se_wgrad_tn_bf16; these two kernels are the sequential
