@@ -358,8 +358,8 @@ int se_mhsa_fwd_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, 
    per-score multiply in front of the exponential, and the running reference starts at 0 (csrc/mhsa.hip, PRE = 1).  Inference only. */
 int se_mhsa_fwd_prescaled_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, void* stream);
 /* Test / measurement surface: the two kernels behind se_mhsa_fwd_prescaled_bf16 by number -- variant 0 = csrc/mhsa.hip (4-wave workgroups, the default
-   below 768 workgroups), 10 = csrc/mhsa8.hip (8-wave workgroups on one LDS-DMA staged tile, the default from there on); bit-identical results.  Other
-   numbers are the parked experiments of tools/experiments/kernels/ (developer builds only): SE_ERR_UNSUPPORTED in the product library. */
+   below 768 workgroups), 10 = csrc/mhsa8.hip (8-wave workgroups on one LDS-DMA staged tile, the default from there on); bit-identical results.  The
+   other numbers of 1 .. 16 belonged to experiments that no longer have a call site (tools/experiments/README.md): SE_ERR_UNSUPPORTED. */
 int se_mhsa_fwd_prescaled_variant_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int variant, void* stream);
 /* Row-complete projection on the encoder's 24-bit residual stream (bf16 hi rows + int8 lo bytes, tile-major: csrc/gemm4.hip), exported for
  * tests / measurement: x = LayerNorm(A . W^T + bias + residual), out as fp32 rows or as (bf16, lo).  variant 0 = the encoder's dispatch,

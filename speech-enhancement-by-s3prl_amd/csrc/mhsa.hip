@@ -19,6 +19,7 @@
 #include "prof.h"
 #include "bf16.h"
 #include "mhsa_tile.h"
+#include "mhsa_route.h"
 #include "dropout.h"
 
 // developer ablation (timing only, results are wrong): build with SE_AMD_EXTRA_DEFINES=-DSE_MHSA_ABL=<mask>: 1 no K/V staging, 2 no barrier,
@@ -39,15 +40,11 @@ namespace se {
 // [2^-60, 2^60) (overflow, inf / nan, or -- first tile -- a row far below the reference) sends the wave to the exact online-softmax tile
 // for this tile and every later one.  fp32 / bf16 keep their relative precision anywhere in that range.  Same box: 133 us speculative
 // against 147 us always-exact (SE_AMD_MHSA_SPEC=0) per B = 32 launch.
-// DMA = 1: the K / V tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write, no wait in front of the writes); the
-// destination of a wave instruction is lane-linear (8 rows x 128 B), so the XOR swizzle of kv_off() is applied to the per-lane SOURCE chunk.
-// The compile-time ablation (-DSE_MHSA_ABL) put the register staging at 27 % of the launch.
-// NW = waves per workgroup (4, or 8 with the register staging only): 8 waves share one staged K / V tile, so each wave stages half as much per tile
-template <int OCC, int DROP, int PRE, int DMA = 0, int NW = 4>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void mhsa_fwd_kernel(
+template <int OCC, int DROP, int PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void mhsa_fwd_kernel(
     const uint16_t* __restrict__ qkv, const int32_t* __restrict__ lengths, int T, int H, uint16_t* __restrict__ ctx,
     float* __restrict__ lse, uint32_t dkey, uint32_t thr16, float dscale) {
-  __shared__ __attribute__((aligned(16))) char smem[(DMA == 2 ? 3 : 2) * 2 * kAK * kHD * 2];   // 2 (DMA == 2: 3) slots x (K, V) x 8 KiB = 32 (48) KiB
+  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * kAK * kHD * 2];   // 2 slots x (K, V) x 8 KiB = 32 KiB
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
@@ -82,8 +79,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
       qt = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
     }
   }
-  static_assert(NW == 4 || (NW == 8 && DMA == 0), "8-wave workgroups: register staging only");
-  const int q0 = qt * (NW * 32) + wave * 32;
+  const int q0 = qt * kAQ + wave * 32;
   const int ld = 3 * H;
   const int len = lengths ? min(max(lengths[b], 1), T) : T;
   const int nkt = (len + kAK - 1) / kAK;
@@ -104,40 +100,24 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
   const uint16_t* kp = kvbase + H + sch * 8;
   const uint16_t* vp = kvbase + 2 * H + sch * 8;
   uint4 rk0, rk1, rv0, rv1;
-  const int so0 = kv_off(srow, sch), so1 = kv_off((srow + 32) & 63, sch);      // NW == 8: 512 threads x 16 B = the whole 64-row tile in one pass
+  const int so0 = kv_off(srow, sch), so1 = kv_off((srow + 32) & 63, sch);
 #define SE_A_ISSUE(kt)                                                                       \
   do {                                                                                       \
     const size_t r0 = (size_t)min((kt) * kAK + srow, T - 1) * ld;                            \
     const size_t r1 = (size_t)min((kt) * kAK + srow + 32, T - 1) * ld;                       \
     rk0 = *reinterpret_cast<const uint4*>(kp + r0);                                          \
-    if (NW == 4) rk1 = *reinterpret_cast<const uint4*>(kp + r1);                             \
+    rk1 = *reinterpret_cast<const uint4*>(kp + r1);                                          \
     rv0 = *reinterpret_cast<const uint4*>(vp + r0);                                          \
-    if (NW == 4) rv1 = *reinterpret_cast<const uint4*>(vp + r1);                             \
+    rv1 = *reinterpret_cast<const uint4*>(vp + r1);                                          \
   } while (0)
 #define SE_A_WRITE(buf)                                                 \
   do {                                                                  \
     char* k_w = smem + (buf) * 16384;                                   \
     char* v_w = k_w + 8192;                                             \
     *reinterpret_cast<uint4*>(k_w + so0) = rk0;                         \
-    if (NW == 4) *reinterpret_cast<uint4*>(k_w + so1) = rk1;            \
+    *reinterpret_cast<uint4*>(k_w + so1) = rk1;                         \
     *reinterpret_cast<uint4*>(v_w + so0) = rv0;                         \
-    if (NW == 4) *reinterpret_cast<uint4*>(v_w + so1) = rv1;            \
-  } while (0)
-  // LDS-DMA form: wave w brings rows [16 w, 16 w + 16) of the K and of the V tile, two 1-KiB pieces (8 rows x 128 B) each; lane l of a piece
-  // writes slot l & 7 of row l >> 3, i.e. it must FETCH chunk (l & 7) ^ f(row) (kv_off: slot = chunk ^ f)
-  typedef __attribute__((address_space(1))) const void* glb_a_t;
-  typedef __attribute__((address_space(3))) void* lds_a_t;
-  const int drow = wave * 16 + (lane >> 3);                 // tile row of this lane in piece 0 (piece 1: + 8)
-  const int dch0 = ((lane & 7) ^ (kv_off(drow, 0) >> 4 & 7)) * 8, dch1 = ((lane & 7) ^ (kv_off(drow + 8, 0) >> 4 & 7)) * 8;
-#define SE_A_DMA(kt, buf)                                                                                                  \
-  do {                                                                                                                     \
-    const size_t r0 = (size_t)min((kt) * kAK + drow, T - 1) * ld;                                                          \
-    const size_t r1 = (size_t)min((kt) * kAK + drow + 8, T - 1) * ld;                                                      \
-    char* k_w = smem + (buf) * 16384 + wave * 2048;                                                                        \
-    __builtin_amdgcn_global_load_lds((glb_a_t)(base + H + r0 + dch0), (lds_a_t)(k_w), 16, 0, 0);                           \
-    __builtin_amdgcn_global_load_lds((glb_a_t)(base + H + r1 + dch1), (lds_a_t)(k_w + 1024), 16, 0, 0);                    \
-    __builtin_amdgcn_global_load_lds((glb_a_t)(base + 2 * H + r0 + dch0), (lds_a_t)(k_w + 8192), 16, 0, 0);                \
-    __builtin_amdgcn_global_load_lds((glb_a_t)(base + 2 * H + r1 + dch1), (lds_a_t)(k_w + 8192 + 1024), 16, 0, 0);         \
+    *reinterpret_cast<uint4*>(v_w + so1) = rv1;                         \
   } while (0)
 
   const f32x16 kZero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -181,24 +161,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
     mw_nxt = *reinterpret_cast<const uint2*>(mrow);
   }
 
-  if (DMA == 2) {
-    // three slots, tiles kt + 1 AND kt + 2 in flight: the first toucher of a K / V tile takes an L2 miss (8 query tiles share it: 12.5 % compulsory
-    // misses), and one tile of lookahead does not cover that round trip under load
-    SE_A_DMA(0, 0);
-    if (nkt > 1) {
-      SE_A_DMA(1, 1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-  } else if (DMA) {
-    SE_A_DMA(0, 0);
-  } else {
-    SE_A_ISSUE(0);
-    SE_A_WRITE(0);
-  }
-  if (DMA != 2) __syncthreads();
+  SE_A_ISSUE(0);
+  SE_A_WRITE(0);
+  __syncthreads();
   SE_STAMP(6);
 
 #ifndef SE_MHSA_PRIO
@@ -209,9 +174,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
 #endif
 #define SE_A_TILE(CUR)                                                                                                     \
   {                                                                                                                        \
-    if (DMA == 2) { if (kt + 2 < nkt) SE_A_DMA(kt + 2, (CUR) >= 1 ? (CUR) - 1 : 2); }                                      \
-    else if (DMA == 3) { if (kt + 1 < nkt) SE_A_DMA(kt + 1, (CUR) ^ 1); }                                                  \
-    else if (kt + 1 < nkt && !(SE_MHSA_ABL & 1)) { if (DMA) SE_A_DMA(kt + 1, (CUR) ^ 1); else SE_A_ISSUE(kt + 1); }       \
+    if (kt + 1 < nkt && !(SE_MHSA_ABL & 1)) SE_A_ISSUE(kt + 1);                                                            \
     uint2 mw_cur = mw_nxt;                                                                                                 \
     if (DROP == 2 && kt + 1 < nkt) mw_nxt = *reinterpret_cast<const uint2*>(mrow + 2 * (kt + 1));                          \
     const char* t_s = smem + (CUR) * 16384;                                                                                \
@@ -338,39 +301,21 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
       }                                                                                                                    \
     if (SE_MHSA_PRIO & 2) __builtin_amdgcn_s_setprio(0);                                                                   \
     SE_STAMP(3);                                                                                                           \
-    if (!DMA && kt + 1 < nkt && !(SE_MHSA_ABL & 1)) SE_A_WRITE((CUR) ^ 1);                                                 \
+    if (kt + 1 < nkt && !(SE_MHSA_ABL & 1)) SE_A_WRITE((CUR) ^ 1);                                                         \
     SE_STAMP(4);                                                                                                           \
-    if (DMA == 2) {                                                                                                        \
-      if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  \
-      __builtin_amdgcn_s_barrier();                                                                                        \
-    } else if (!(SE_MHSA_ABL & 2)) __syncthreads();                                                                        \
+    if (!(SE_MHSA_ABL & 2)) __syncthreads();                                                                               \
     SE_STAMP(5);                                                                                                           \
   }
 
+  // unrolled by two so the double-buffer offset is an immediate
   int kt = 0;
-  if (DMA == 2) {
-    // ONE tile body with a run-time slot (three unrolled bodies spill at 3 waves per SIMD)
-    int slot = 0;
-    for (; kt < nkt; ++kt) {
-      SE_A_TILE(slot)
-      slot = slot == 2 ? 0 : slot + 1;
-    }
-  } else if (DMA == 3) {
-    int slot = 0;
-    for (; kt < nkt; ++kt) {
-      SE_A_TILE(slot)
-      slot ^= 1;
-    }
-  } else {
-    // unrolled by two so the double-buffer offset is an immediate
-    for (; kt + 1 < nkt; kt += 2) {
-      SE_A_TILE(0)
-      ++kt;
-      SE_A_TILE(1)
-      --kt;
-    }
-    if (kt < nkt) SE_A_TILE(0)
+  for (; kt + 1 < nkt; kt += 2) {
+    SE_A_TILE(0)
+    ++kt;
+    SE_A_TILE(1)
+    --kt;
   }
+  if (kt < nkt) SE_A_TILE(0)
 #undef SE_A_TILE
 
   // ---- epilogue: O / l ; lane holds query q0 + l31, d = 32 dblk + (r&3) + 8 (r>>2) + 4 hh
@@ -398,7 +343,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
   if (PRE && lse) {
     st_acc[7] = __builtin_amdgcn_s_memtime() - st_t0;
     const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    unsigned long long* sp = reinterpret_cast<unsigned long long*>(lse) + ((size_t)lin * NW + wave) * 8;
+    unsigned long long* sp = reinterpret_cast<unsigned long long*>(lse) + ((size_t)lin * 4 + wave) * 8;
     if (lane == 0) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) sp[i] = st_acc[i];
@@ -410,95 +355,83 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
 
 }  // namespace se
 
-int se_mhsaN_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, int nw, int wpe, hipStream_t st);   // mhsa8.hip
-#ifdef SE_AMD_EXPERIMENTS      // the parked attention forwards (tools/experiments/kernels/, mhsa8.hip's other layouts): developer builds only
-int se_mhsa_fwd_pipe_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int occ, hipStream_t st);   // mhsa_pipe.hip
-int se_mhsa2_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, hipStream_t st);   // mhsa2.hip
-int se_mhsa3_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, hipStream_t st);   // mhsa3.hip
-int se_mhsa8_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, hipStream_t st);   // mhsa8.hip
-int se_mhsa9_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, hipStream_t st);   // mhsa9.hip
-int se_mhsaP_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int never_speculate, int wgs, hipStream_t st);   // mhsa8.hip
-#endif
+int se_mhsa_wave8_fwd_launch(const se::MhsaCall& call, dim3 grid, dim3 block, const uint16_t* qkv, const int32_t* lengths, uint16_t* ctx, float dscale,
+                             hipStream_t st);   // mhsa8.hip
 
-static int mhsa_fwd_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, float* lse, float dropout_p,
-                           uint64_t seed, uint32_t site, void* stream) {
-  SE_REQUIRE(qkv && ctx, "se_mhsa_fwd_bf16: null argument");
-  SE_REQUIRE(B > 0 && B <= 65535 && T > 0 && heads > 0 && heads <= 65535, "se_mhsa_fwd_bf16: bad shape B=%d T=%d heads=%d", B, T, heads);
-  const int H = heads * se::kHD;
-  dim3 grid((T + se::kAQ - 1) / se::kAQ, heads, B);
-  se::ProfScope prof(se::kProfMhsa, 4.0 * B * (double)heads * T * (double)T * se::kHD, se::as_stream(stream));
-  static int occ = -1;
-  if (occ < 0) {
-    const char* e = getenv("SE_AMD_MHSA_OCC");
-    occ = e ? atoi(e) : 3;
-  }
+static_assert(se::kAQ == se::kMhsaWave4Rows, "mhsa_route.h: query rows per workgroup of this file's kernel");
+
+static bool mhsa_shape_ok(int B, int T, int heads) { return B > 0 && B <= 65535 && T > 0 && heads > 0 && heads <= 65535; }
+
+// The one launch site of the four public entries: argument checks -> MhsaCall -> mhsa_route() -> switch.  `entry` names the caller in the
+// messages; variant >= 0 (the variant entry) takes the place of SE_AMD_MHSA_PIPE.
+static int mhsa_launch(const char* entry, const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, float* lse, bool prescaled,
+                       int variant, float dropout_p, uint64_t seed, uint32_t site, void* stream) {
+  SE_REQUIRE(qkv && ctx, "%s: null argument", entry);
+  SE_REQUIRE(mhsa_shape_ok(B, T, heads), "%s: bad shape B=%d T=%d heads=%d", entry, B, T, heads);
   const se::DropoutCfg d = se::make_dropout(dropout_p, seed);
-  if (d.thr16) {
-    SE_REQUIRE((double)B * heads * T * ((T + 1) / 2) < 4294967296.0, "se_mhsa_fwd: dropout pair index exceeds 32 bits");
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 1, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, lse,
-                       se::dropout_key(seed, site), d.thr16, d.scale);
-  } else if (occ == 2) {
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 0, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, lse, 0u, 0u, 1.f);
-  } else {
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, lse, 0u, 0u, 1.f);
+  const se::MhsaCall call{B, T, heads, prescaled, d.thr16 != 0};
+  se::MhsaTuning tuning = se::mhsa_tuning();
+  if (variant >= 0) tuning.force_variant = variant;
+  if (prescaled && tuning.force_variant >= 0 && !se::mhsa_variant_ok(tuning.force_variant)) {
+    se::set_error("se_mhsa_fwd_prescaled: variant %d is a parked experiment (developer builds: SE_AMD_BUILD_EXPERIMENTS=kernels); the product has 0 and 10",
+                  tuning.force_variant);
+    return SE_ERR_UNSUPPORTED;
+  }
+  const se::MhsaRoute route = se::mhsa_route(call, tuning);
+  const se::MhsaGrid g = se::mhsa_grid(route);
+  const dim3 grid((T + g.rows - 1) / g.rows, heads, B), block(g.threads);
+  const int H = heads * se::kHD;
+  hipStream_t st = se::as_stream(stream);
+  se::ProfScope prof(se::kProfMhsa, 4.0 * B * (double)heads * T * (double)T * se::kHD, st);
+  const float spec = tuning.speculate ? 1.f : -1.f;      // dscale < 0: the prescaled kernels never speculate
+  switch (route) {
+    case se::MhsaRoute::Wave4:
+      hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 0>), grid, block, 0, st, qkv, lengths, T, H, ctx, lse, 0u, 0u, 1.f);
+      break;
+    case se::MhsaRoute::Wave4Dropout:
+      SE_REQUIRE(se::mhsa_wave4_dropout_ok(call), "se_mhsa_fwd: dropout pair index exceeds 32 bits");
+      hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 1, 0>), grid, block, 0, st, qkv, lengths, T, H, ctx, lse, se::dropout_key(seed, site), d.thr16, d.scale);
+      break;
+    case se::MhsaRoute::Wave4Prescaled:
+      hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1>), grid, block, 0, st, qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec);
+      break;
+    case se::MhsaRoute::Wave8Prescaled:
+      return se_mhsa_wave8_fwd_launch(call, grid, block, qkv, lengths, ctx, spec, st);
   }
   SE_LAUNCH_CHECK();
   return SE_OK;
 }
 
 extern "C" int se_mhsa_fwd_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, void* stream) {
-  return mhsa_fwd_launch(qkv, lengths, B, T, heads, ctx, nullptr, 0.f, 0, 0, stream);
+  return mhsa_launch("se_mhsa_fwd_bf16", qkv, lengths, B, T, heads, ctx, nullptr, false, -1, 0.f, 0, 0, stream);
 }
 
-static int mhsa_prescaled_launch(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int pipe, void* stream) {
-  SE_REQUIRE(qkv && ctx, "se_mhsa_fwd_prescaled_bf16: null argument");
-  SE_REQUIRE(B > 0 && B <= 65535 && T > 0 && heads > 0 && heads <= 65535, "se_mhsa_fwd_prescaled_bf16: bad shape B=%d T=%d heads=%d", B, T, heads);
-  const int H = heads * se::kHD;
-  dim3 grid((T + se::kAQ - 1) / se::kAQ, heads, B);
-  se::ProfScope prof(se::kProfMhsa, 4.0 * B * (double)heads * T * (double)T * se::kHD, se::as_stream(stream));
-  static int spec = -1;
-  if (spec < 0) { const char* e = getenv("SE_AMD_MHSA_SPEC"); spec = e ? atoi(e) : 1; }      // 0: always the exact online-softmax tile (A/B)
-  // 10: 8 free-running waves on one LDS-DMA staged tile, two workgroups per CU, waves 4-7 half a tile behind (mhsa8.hip; the default from 768 workgroups on)
-  if (pipe == 10) return se_mhsaN_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, 8, 4, se::as_stream(stream));
-#ifdef SE_AMD_EXPERIMENTS
-  static int pipe_occ = -1;
-  if (pipe_occ < 0) {
-    const char* o = getenv("SE_AMD_MHSA_PIPE_OCC");
-    pipe_occ = o ? atoi(o) : 2;
-  }
-  if (pipe == 1) return se_mhsa_fwd_pipe_launch(qkv, lengths, B, T, heads, ctx, pipe_occ, se::as_stream(stream));
-  if (pipe == 12) return se_mhsa9_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, se::as_stream(stream));      // 8 waves, software-pipelined over the key tiles (mhsa9.hip)
-  if (pipe == 11 || pipe == 13 || pipe == 14)      // variant 10 as persistent workgroups (mhsa8.hip); 13 / 14: with 8 / 5 workgroups (tests: long item lists, both list forms)
-    return se_mhsaP_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, pipe == 11 ? 0 : (pipe == 13 ? 8 : 5), se::as_stream(stream));
-  if (pipe == 9 || pipe == 16) return se_mhsaN_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, pipe == 16 ? 16 : 8, pipe == 9 ? 2 : 4, se::as_stream(stream));
-  if (pipe == 8) return se_mhsa8_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, se::as_stream(stream));      // 8-wave alternating segments (mhsa8.hip)
-  if (pipe == 3) return se_mhsa3_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, se::as_stream(stream));      // interleaved matrix / vector stream, two query blocks per wave (mhsa3.hip)
-  if (pipe == 2) return se_mhsa2_fwd_launch(qkv, lengths, B, T, heads, ctx, spec ? 0 : 1, se::as_stream(stream));      // two query blocks per wave (mhsa2.hip)
-  static int dma = -1;
-  if (dma < 0) { const char* e = getenv("SE_AMD_MHSA_DMA"); dma = e ? atoi(e) : 0; }        // A/B: LDS-DMA rings inside this file's kernel (all measured equal or slower)
-  static int nw8 = -1;
-  if (nw8 < 0) { const char* e = getenv("SE_AMD_MHSA_NW"); nw8 = (e && atoi(e) == 8) ? 1 : 0; }      // A/B: 8-wave workgroups (256 queries share a staged tile)
-  if (dma == 3)
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<4, 0, 1, 3>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  else if (dma == 4)
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1, 3>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  else if (dma == 2)
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1, 2>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  else if (dma)
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1, 1>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  else if (nw8) {
-    dim3 grid8((T + 255) / 256, heads, B);
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 0, 1, 0, 8>), grid8, dim3(512), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  } else
-#else
-  if (pipe != 0) {
-    se::set_error("se_mhsa_fwd_prescaled: variant %d is a parked experiment (developer builds: SE_AMD_BUILD_EXPERIMENTS=kernels); the product has 0 and 10", pipe);
-    return SE_ERR_UNSUPPORTED;
-  }
-#endif
-    hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, nullptr, 0u, 0u, spec ? 1.f : -1.f);
-  SE_LAUNCH_CHECK();
-  return SE_OK;
+extern "C" int se_mhsa_fwd_lse_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, float* lse,
+                                    float dropout_p, uint64_t seed, uint32_t site, void* stream) {
+  SE_REQUIRE(lse, "se_mhsa_fwd_lse_bf16: null lse");
+  return mhsa_launch("se_mhsa_fwd_bf16", qkv, lengths, B, T, heads, ctx, lse, false, -1, dropout_p, seed, site, stream);
+}
+
+extern "C" int se_mhsa_fwd_prescaled_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, void* stream) {
+  return mhsa_launch("se_mhsa_fwd_prescaled_bf16", qkv, lengths, B, T, heads, ctx, nullptr, true, -1, 0.f, 0, 0, stream);
+}
+
+// test / measurement surface: variant 0 = this file's kernel (the default below 768 workgroups), 10 = mhsa8.hip's (the default from there on)
+extern "C" int se_mhsa_fwd_prescaled_variant_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int variant,
+                                                  void* stream) {
+  SE_REQUIRE(variant >= 0 && variant <= 16, "se_mhsa_fwd_prescaled_variant_bf16: variant %d (0 or 10)", variant);
+  return mhsa_launch("se_mhsa_fwd_prescaled_bf16", qkv, lengths, B, T, heads, ctx, nullptr, true, variant, 0.f, 0, 0, stream);
+}
+
+// internal (tests; not in se_amd.h): the route of a call under the default tuning, as the int value of MhsaRoute, or the error the call itself
+// would return -- no device is touched
+extern "C" int se_mhsa_route_of(int B, int T, int heads, int prescaled, int dropout) {
+  SE_REQUIRE(mhsa_shape_ok(B, T, heads) && !(prescaled && dropout), "se_mhsa_route_of: not a valid attention forward call (B=%d T=%d heads=%d prescaled=%d dropout=%d)",
+             B, T, heads, prescaled, dropout);
+  const se::MhsaCall call{B, T, heads, prescaled != 0, dropout != 0};
+  const se::MhsaRoute route = se::mhsa_route(call, se::MhsaTuning{});
+  SE_REQUIRE(se::mhsa_route_ok(route, call), "se_mhsa_route_of: route %d cannot run B=%d T=%d heads=%d (the call fails)", static_cast<int>(route), B, T, heads);
+  return static_cast<int>(route);
 }
 
 #ifdef SE_AMD_STAMPS
@@ -508,41 +441,13 @@ extern "C" int se_mhsa_fwd_stamps_bf16(const uint16_t* qkv, const int32_t* lengt
   const int H = heads * se::kHD;
   dim3 grid((T + se::kAQ - 1) / se::kAQ, heads, B);
   float* sp = reinterpret_cast<float*>(stamps);
-  if (occ == 1) hipLaunchKernelGGL((se::mhsa_fwd_kernel<1, 0, 1, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
-  else if (occ == 2) hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 0, 1, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
-  else hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1, 0>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
+  if (occ == 1) hipLaunchKernelGGL((se::mhsa_fwd_kernel<1, 0, 1>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
+  else if (occ == 2) hipLaunchKernelGGL((se::mhsa_fwd_kernel<2, 0, 1>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
+  else hipLaunchKernelGGL((se::mhsa_fwd_kernel<3, 0, 1>), grid, dim3(256), 0, se::as_stream(stream), qkv, lengths, T, H, ctx, sp, 0u, 0u, 1.f);
   SE_LAUNCH_CHECK();
   return SE_OK;
 }
 #endif
-
-extern "C" int se_mhsa_fwd_prescaled_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, void* stream) {
-  static int pipe = -2, min_wgs = 768;
-  if (pipe == -2) {
-    const char* e = getenv("SE_AMD_MHSA_PIPE");
-    pipe = e ? atoi(e) : -1;     // A/B: force one variant (0 = this file's kernel, 10 = mhsa8.hip's; developer builds: the parked experiments too)
-    if (const char* m = getenv("SE_AMD_MHSA8_MIN_WGS")) min_wgs = atoi(m);
-  }
-  if (pipe >= 0) return mhsa_prescaled_launch(qkv, lengths, B, T, heads, ctx, pipe, stream);
-  // default (round 4): 8-wave workgroups on one LDS-DMA staged K / V tile, two per CU, half of each SIMD's waves half a tile behind (mhsa8.hip:
-  // mhsaN_fwd_kernel<8, 4, 1>; 107 vs 118 us at B = 32) from 768 such workgroups (1.5 per CU slot pair) on -- B >= 16 at T = 1001; below that this
-  // file's 4-wave workgroups (three per CU, twice as many of them) cover the CUs better (profiles/r04_mhsa_bsweep.txt)
-  const long wgs8 = (long)((T + 255) / 256) * heads * B;
-  return mhsa_prescaled_launch(qkv, lengths, B, T, heads, ctx, wgs8 >= min_wgs ? 10 : 0, stream);
-}
-
-// test / measurement surface: variant 0 = this file's kernel (the default below 768 workgroups), 10 = mhsa8.hip's (the default from there on)
-extern "C" int se_mhsa_fwd_prescaled_variant_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, int variant,
-                                                  void* stream) {
-  SE_REQUIRE(variant >= 0 && variant <= 16, "se_mhsa_fwd_prescaled_variant_bf16: variant %d (0 or 10)", variant);
-  return mhsa_prescaled_launch(qkv, lengths, B, T, heads, ctx, variant, stream);
-}
-
-extern "C" int se_mhsa_fwd_lse_bf16(const uint16_t* qkv, const int32_t* lengths, int B, int T, int heads, uint16_t* ctx, float* lse,
-                                    float dropout_p, uint64_t seed, uint32_t site, void* stream) {
-  SE_REQUIRE(lse, "se_mhsa_fwd_lse_bf16: null lse");
-  return mhsa_fwd_launch(qkv, lengths, B, T, heads, ctx, lse, dropout_p, seed, site, stream);
-}
 
 #ifdef SE_AMD_EXPERIMENTS
 // Training forward with the dropout mask of dropmask.hip (se_mhsa_dropmask: query-major bit matrix `mask_r`) instead of the in-kernel hash: same

@@ -189,7 +189,7 @@ def test_mhsa_vs_torch(gpu, B, T, heads, lens):
 @pytest.mark.parametrize('B,T,heads,lens', [(2, 1001, 12, None), (3, 300, 4, [300, 17, 129]), (1, 64, 1, None), (2, 130, 2, [1, 65]), (8, 257, 1, [257, 200, 64, 63, 1, 128, 129, 256])])
 @pytest.mark.parametrize('variant', [0, 10])
 def test_mhsa_prescaled_vs_torch(gpu, B, T, heads, lens, variant):
-    """the inference kernel on pre-scaled queries (variant 0) and the software-pipelined half-tile experiment (variant 1, csrc/mhsa_pipe.hip)
+    """the two inference kernels on pre-scaled queries (variant 0: csrc/mhsa.hip's 4-wave kernel, variant 10: csrc/mhsa8.hip's 8-wave kernel)
     vs fp64 on the SAME bf16 operands: softmax_base2(Q' K^T) V with Q' = bf16(Q log2(e) / 8)"""
     L = _lib()
     lib = L.load()
@@ -214,6 +214,52 @@ def test_mhsa_prescaled_vs_torch(gpu, B, T, heads, lens, variant):
     err = (got - ref).abs()
     assert torch.isfinite(got).all()
     assert err.max().item() < 8e-3 * ref.abs().max().item(), err.max().item()      # P and the output are rounded to bf16 (2^-9 relative)
+
+
+MHSA_ROUTES = ('Wave4', 'Wave4Dropout', 'Wave4Prescaled', 'Wave8Prescaled')      # csrc/mhsa_route.h
+
+
+@pytest.mark.parametrize('B,T,heads,route', [
+    (768, 64, 1, 'Wave8Prescaled'),      # 768 8-wave workgroups, pairs % 8 == 0: the XCD mapping
+    (767, 64, 1, 'Wave4Prescaled'),      # 767: below the threshold, the plain mapping
+    (192, 257, 2, 'Wave8Prescaled'),     # 2 query tiles x 2 heads x 192 = 768, ragged second query tile
+    (191, 257, 2, 'Wave4Prescaled'),     # 764
+])
+def test_mhsa_prescaled_default_dispatch(gpu, B, T, heads, route):
+    """se_mhsa_fwd_prescaled_bf16 (the encoder's entry) on both sides of its threshold at the smallest shapes that cross it, ragged lengths
+    including 1: bit-identical to the variant entry that se_mhsa_route_of names, and within test_mhsa_prescaled_vs_torch's bound of fp64"""
+    import ctypes
+    L = _lib()
+    lib = L.load()
+    fn = lib.se_mhsa_route_of
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 5
+    got = fn(B, T, heads, 1, 0)
+    assert 0 <= got < len(MHSA_ROUTES) and MHSA_ROUTES[got] == route, (got, L.last_error())
+    variant = {'Wave4Prescaled': 0, 'Wave8Prescaled': 10}[route]
+    torch.manual_seed(B + T)
+    H = heads * 64
+    x = torch.randn(B * T, 3 * H, device=gpu) * 1.5
+    x[:, :H] *= 1.4426950408889634 / 8.0
+    qkv = x.bfloat16()
+    lengths = (1 + (torch.arange(B, device=gpu) * 37) % T).to(torch.int32)      # 1, 38, 75, ... in [1, T]
+    lengths[1] = T
+    assert lengths.min().item() == 1 and lengths.max().item() == T
+    ctx = torch.full((B * T, H), float('nan'), device=gpu, dtype=torch.bfloat16)
+    ctx_v = torch.full((B * T, H), float('nan'), device=gpu, dtype=torch.bfloat16)
+    L.check(lib.se_mhsa_fwd_prescaled_bf16(L.ptr(qkv), L.ptr(lengths), B, T, heads, L.ptr(ctx), L.stream()), 'se_mhsa_fwd_prescaled_bf16')
+    L.check(lib.se_mhsa_fwd_prescaled_variant_bf16(L.ptr(qkv), L.ptr(lengths), B, T, heads, L.ptr(ctx_v), variant, L.stream()),
+            'se_mhsa_fwd_prescaled_variant_bf16')
+    assert torch.isfinite(ctx.float()).all()
+    assert torch.equal(ctx, ctx_v)
+    q = qkv.double().reshape(B, T, 3, heads, 64)
+    Q, K, V = q[:, :, 0].transpose(1, 2), q[:, :, 1].transpose(1, 2), q[:, :, 2].transpose(1, 2)
+    S = (Q @ K.transpose(-1, -2)) * 0.6931471805599453                       # bits -> nats
+    mask = torch.arange(T, device=gpu)[None, :] >= lengths[:, None].long()
+    S = S.masked_fill(mask[:, None, None, :], float('-inf'))
+    ref = (torch.softmax(S, dim=-1) @ V).transpose(1, 2).reshape(B * T, H)
+    err = (ctx.double() - ref).abs().max().item()
+    assert err < 8e-3 * ref.abs().max().item(), err      # P and the output are rounded to bf16 (2^-9 relative)
 
 
 @pytest.mark.parametrize('variant', [0, 10])

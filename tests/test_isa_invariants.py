@@ -63,7 +63,7 @@ def test_wgrad_ring_is_not_drained_by_the_compiler(tmp_path, stag):
     ('gemm6.hip', '_ZN2se18gemm6p_bf16_kernelILi0ELi2ELi0EE', []),          # persistent 256 x 256 GEMM (QKV)
     ('gemm6.hip', '_ZN2se18gemm6p_bf16_kernelILi3ELi2ELi0EE', []),          # ... with the GELU epilogue (FFN1)
     ('gemm4.hip', '_ZN2se19gemm7_res_ln_kernelILi0ELi1ELi1ELi1ELi1ELi0EE', []),   # row-complete GEMM + residual + LayerNorm on the 24-bit stream
-    ('mhsa8.hip', '_ZN2se16mhsaN_fwd_kernelILi8ELi4ELi1EE', ['-fno-slp-vectorize']),   # the inference attention forward
+    ('mhsa8.hip', '_ZN2se21mhsa_wave8_fwd_kernelE', ['-fno-slp-vectorize']),   # the inference attention forward
 ])
 def test_hot_lds_dma_loops_are_not_drained_by_the_compiler(tmp_path, src, prefix, flags):
     """the other LDS-DMA kernels of the inference pass: same property (their DMA is inline asm, their waits are counted by hand)"""

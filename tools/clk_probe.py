@@ -75,7 +75,7 @@ qkv = torch.randn(M, 3 * H, device=dev)
 qkv[:, :H] *= 1.4426950408889634 / 8.0
 qkv = qkv.bfloat16()
 ctx = torch.empty(M, H, device=dev, dtype=torch.bfloat16)
-run('attention forward (mhsaN<8,4,1>) B=32 T=1001', 'clkprobe_mhsa',
+run('attention forward (mhsa_wave8_fwd_kernel) B=32 T=1001', 'clkprobe_mhsa',
     lambda: L.check(lib.se_mhsa_fwd_prescaled_variant_bf16(L.ptr(qkv), None, B, T, heads, L.ptr(ctx), 10, L.stream()), 'mhsa'), 4.0 * B * heads * T * T * 64)
 
 x = torch.randn(M, 3072, device=dev).bfloat16()

@@ -47,27 +47,3 @@ for occ in (1, 2, 3):
         pw = full[:, w, :6].mean(0) / ntile
         print(f'    wave {w}: ' + ' '.join(f'{v:6.0f}' for v in pw.tolist()))
 
-
-# ---- the 8-wave alternating kernel (mhsa8.hip): cycles per segment and per barrier wait, waves 0-3 (one segment ahead) and 4-7 apart
-fn8 = lib.se_mhsa8_fwd_stamps_bf16
-fn8.restype = ctypes.c_int
-fn8.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3
-nwg8 = ((T + 255) // 256) * heads * B
-st = torch.zeros(nwg8 * 8 * 10, device=dev, dtype=torch.int64)
-for _ in range(3):
-    L.check(fn8(L.ptr(q), None, B, T, heads, L.ptr(ctx), L.ptr(st), L.stream()), 'stamps8')
-torch.cuda.synchronize()
-a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-a.record()
-for _ in range(10):
-    L.check(fn8(L.ptr(q), None, B, T, heads, L.ptr(ctx), L.ptr(st), L.stream()), 'stamps8')
-b.record()
-torch.cuda.synchronize()
-s = st.view(nwg8, 8, 10).double()
-seg = ['C1 (QK^T)', 'barrier', 'L1 (V reads, softmax, DMA)', 'barrier', 'C2 (PV)', 'barrier', 'L2 (K reads)', 'barrier']
-print(f'--- mhsa8: launch {a.elapsed_time(b) / 10 * 1e3:.1f} us (stamp build); cycles per 64-key tile, mean over workgroups')
-for grp, sl in (('waves 0-3', slice(0, 4)), ('waves 4-7', slice(4, 8))):
-    per = s[:, sl, :8].mean((0, 1)) / 16.0
-    print(f'  {grp}: total {per.sum().item():.0f}; loop {s[:, sl, 8].mean().item():.0f} cycles')
-    for i in range(8):
-        print(f'      {seg[i]:28s} {per[i].item():7.0f}')
