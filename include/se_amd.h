@@ -193,6 +193,31 @@ int se_dbnorm_f32(float* wav, int B, int T, int wav_stride, const int64_t* lengt
                   const float* wav_sumsq, const float* ref_sumsq, float fixed_db, float eps, void* stream);
 
 /*
+ * se_dbnorm_bwd_f32 -- the backward of se_dbnorm_f32 (utils.py:31-46 differentiated; no gradient flows to a reference waveform).  wav_norm is the
+ * normalised output y = scale wav the forward left in place, grad_out its gradient g, the sums and (ref_sumsq, fixed_db, eps) as the forward's:
+ *   grad_wav[n] = scale g[n] - [n < len] y[n] (sum_{n' < T} g[n'] y[n']) / (scale M (len + eps)),   M = wav_sumsq / (len + eps) + eps
+ * (the sum in fp64 per utterance in `scratch`, device double[B], cleared inside; scale = 0 -- a silent reference -- gives scale g).
+ * grad_wav (B, wav_stride) may alias grad_out.  A negative length is an empty mask, as in the forward.
+ */
+int se_dbnorm_bwd_f32(const float* wav_norm, const float* grad_out, int B, int T, int wav_stride, const int64_t* lengths,
+                      const float* wav_sumsq, const float* ref_sumsq, float fixed_db, float eps, double* scratch, float* grad_wav,
+                      void* stream);
+
+/*
+ * se_istft_bwd_f32 -- the backward of row A6, OnlinePreprocessor.istft (runner.py:267), as se_istft_f32 (phase, fp32 radians) and
+ * se_istft_tphase_f32 (tphase, encoded words) compute it with linear_power = 2 and a power plane (no log_input): exactly one of phase and
+ * tphase is non-NULL, and it is held fixed (the decode uses the noisy phase).  grad_wav (B, wav_stride) = d loss / d wav_out ->
+ * grad_power (B, F, K) = d loss / d power, fully written (no accumulation), and exactly 0 where power <= 0 (a stated subgradient: torch's
+ * pow(0.5) gives inf / nan there, and the zero-padded frames of a ragged batch have power 0).  The adjoint is a forward STFT of the
+ * envelope-divided gradient with ZERO padding (the envelope with the inverse transform's edge rule); one kernel for both plan kinds (a plan of
+ * se_plan_create builds the general tables of its geometry at creation).  Asynchronous, allocates nothing, no atomics: repeats are bit-identical.
+ * se_istft_bwd_chunk_frames: frames per workgroup of that kernel (for tests that want to straddle workgroup borders); -1 for NULL.
+ */
+int se_istft_bwd_f32(const se_plan* plan, const float* grad_wav, int wav_stride, const float* power, const float* phase,
+                     const unsigned* tphase, int B, int F, float* grad_power, void* stream);
+int se_istft_bwd_chunk_frames(const se_plan* plan);
+
+/*
  * se_length_masks_i64 -- row D1: Runner._get_length_masks (runner.py:216-220): masks[b,t] = t < lengths[b] (int64).
  */
 int se_length_masks_i64(const int64_t* lengths, int B, int max_len, int64_t* masks, void* stream);
@@ -542,6 +567,11 @@ int se_mix_f32(const float* speech, int ld_s, const int64_t* len_s, const float*
  * src, tar (B, ld) fp32; sums: device double[3 B] scratch; sisdr (B) fp32 in dB. */
 int se_sisdr_f32(const float* src, const float* tar, int ld, const int64_t* lengths, int B, float eps, double* sums, float* sisdr,
                  void* stream);
+/* The gradient of that score (evaluation.py:5-10 differentiated; the reference's objective.py:16-45 declares criteria on wav_predicted / wav_tar):
+ * grad (B, ld) = grad_scale * d sisdr_b / d src = grad_scale (p_b tar + q_b src) for n < lengths[b], zeros from there out to ld.  `sums` as
+ * se_sisdr_f32 left them for the same src, tar, lengths and eps; p_b, q_b are two fp64 coefficients per utterance. */
+int se_sisdr_grad_f32(const float* src, const float* tar, int ld, const int64_t* lengths, int B, float eps, const double* sums,
+                      float grad_scale, float* grad, void* stream);
 
 /* evaluation.stoi_eval / estoi_eval (evaluation.py:28-36: pystoi.stoi(tar, src, sr, extended)) for each utterance over its first lengths[b]
  * samples (runner.py:597-603), on the device.  The signal chain is restated here, not linked: parity unpinned vs pystoi.

@@ -76,6 +76,9 @@ SIGNATURES = {
     'se_istft_f32': (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P, _P]),
     'se_masked_sumsq_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     'se_dbnorm_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P]),
+    'se_dbnorm_bwd_f32': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P]),
+    'se_istft_bwd_f32': (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
+    'se_istft_bwd_chunk_frames': (c_int, [_P]),
     'se_length_masks_i64': (c_int, [_P, c_int, c_int, _P, _P]),
     'se_head_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'se_head_linear_f32': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
@@ -146,6 +149,7 @@ SIGNATURES = {
     'se_multi_copy_f32': (c_int, [_P, _P, _P, c_int, _P]),
     'se_mix_f32': (c_int, [_P, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P]),
     'se_sisdr_f32': (c_int, [_P, _P, c_int, _P, c_int, c_float, _P, _P, _P]),
+    'se_sisdr_grad_f32': (c_int, [_P, _P, c_int, _P, c_int, c_float, _P, c_float, _P, _P]),
     'se_stoi_plan_create': (c_int, [c_int, POINTER(_P)]),
     'se_stoi_plan_destroy': (None, [_P]),
     'se_stoi_workspace_bytes': (c_size_t, [_P, c_int, c_int]),

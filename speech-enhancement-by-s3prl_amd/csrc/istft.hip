@@ -283,6 +283,45 @@ __global__ __launch_bounds__(256) void dbnorm_kernel(float* __restrict__ wav, in
   for (int n = blockIdx.x * 256 + threadIdx.x; n < T; n += gridDim.x * 256) row[n] *= scale;
 }
 
+// ---- the backward of dbnorm_kernel (utils.py:31-46 differentiated; the reference waveform is a constant).  With y = scale wav the output the
+// forward left in place and g its gradient:  d wav[n] = scale g[n] - [n < len] y[n] (sum_n' g y) / (scale M (len + eps)),  M = S / (len + eps) + eps
+// (d scale / d wav[n] = -[n < len] scale wav[n] / (M (len + eps)), and sum g wav = (sum g y) / scale).  Reduce: dot[b] = sum_{n < T} g y in fp64.
+__global__ __launch_bounds__(256) void dbnorm_bwd_dot_kernel(const float* __restrict__ y, const float* __restrict__ g, int T, int wav_stride,
+                                                             double* __restrict__ dot) {
+  __shared__ double red[4];
+  const int b = blockIdx.y;
+  const float* yr = y + (size_t)b * wav_stride;
+  const float* gr = g + (size_t)b * wav_stride;
+  double acc = 0.0;
+  for (int n = blockIdx.x * 256 + threadIdx.x; n < T; n += gridDim.x * 256) acc += (double)yr[n] * (double)gr[n];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(&dot[b], (red[0] + red[1]) + (red[2] + red[3]));
+}
+
+__global__ __launch_bounds__(256) void dbnorm_bwd_apply_kernel(const float* __restrict__ y, const float* g, int T, int wav_stride,
+                                                               const int64_t* __restrict__ lengths, const float* __restrict__ wav_sumsq,
+                                                               const float* __restrict__ ref_sumsq, float fixed_db, float eps,
+                                                               const double* __restrict__ dot, float* grad_wav) {
+  const int b = blockIdx.y;
+  const int len = (int)min((int64_t)T, max((int64_t)0, lengths[b]));       // a negative length is an empty mask, as in the forward
+  const double denom = (double)((float)len + eps);
+  const double R = ref_sumsq ? (double)ref_sumsq[b] / denom : pow(10.0, (double)fixed_db / 10.0);
+  const double M = (double)wav_sumsq[b] / denom + (double)eps;
+  const double sc = sqrt(R / M);
+  const float scale = (float)sc;
+  const float coef = sc > 0.0 ? (float)(dot[b] / (sc * M * denom)) : 0.f;     // scale = 0 (a silent reference): y = 0 and d scale / d wav = 0
+  const float* yr = y + (size_t)b * wav_stride;
+  const float* gr = g + (size_t)b * wav_stride;
+  float* o = grad_wav + (size_t)b * wav_stride;
+  for (int n = blockIdx.x * 256 + threadIdx.x; n < T; n += gridDim.x * 256) {
+    const float gv = gr[n], yv = yr[n];      // both read before the store: grad_wav may alias g
+    o[n] = (n < len) ? fmaf(-yv, coef, scale * gv) : scale * gv;
+  }
+}
+
 __global__ void length_masks_kernel(const int64_t* __restrict__ lengths, int max_len, int64_t* __restrict__ masks) {
   const int b = blockIdx.y;
   const int64_t len = lengths[b];
@@ -380,6 +419,22 @@ extern "C" int se_dbnorm_f32(float* wav, int B, int T, int wav_stride, const int
   dim3 grid(std::min(64, (T + 255) / 256), B);
   hipLaunchKernelGGL(se::dbnorm_kernel, grid, dim3(256), 0, se::as_stream(stream), wav, T, wav_stride, lengths, wav_sumsq,
                      ref_sumsq, fixed_db, eps);
+  SE_LAUNCH_CHECK();
+  return SE_OK;
+}
+
+extern "C" int se_dbnorm_bwd_f32(const float* wav_norm, const float* grad_out, int B, int T, int wav_stride, const int64_t* lengths,
+                                 const float* wav_sumsq, const float* ref_sumsq, float fixed_db, float eps, double* scratch, float* grad_wav,
+                                 void* stream) {
+  SE_REQUIRE(wav_norm && grad_out && lengths && wav_sumsq && scratch && grad_wav && B > 0 && B <= 65535 && T > 0 && wav_stride >= T,
+             "se_dbnorm_bwd_f32: bad argument");
+  hipStream_t st = se::as_stream(stream);
+  { const int zrc_ = se::zero_async(scratch, sizeof(double) * B, st); if (zrc_) return zrc_; }
+  hipLaunchKernelGGL(se::dbnorm_bwd_dot_kernel, dim3(std::max(1, std::min(64, (T + 4095) / 4096)), B), dim3(256), 0, st, wav_norm, grad_out, T,
+                     wav_stride, scratch);
+  SE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(se::dbnorm_bwd_apply_kernel, dim3(std::min(64, (T + 255) / 256), B), dim3(256), 0, st, wav_norm, grad_out, T, wav_stride,
+                     lengths, wav_sumsq, ref_sumsq, fixed_db, eps, scratch, grad_wav);
   SE_LAUNCH_CHECK();
   return SE_OK;
 }

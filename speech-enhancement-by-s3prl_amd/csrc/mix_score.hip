@@ -124,7 +124,42 @@ __global__ void sisdr_final_kernel(const double* __restrict__ sums, int B, float
   out[b] = (float)(10.0 * log10(ay2 / (err + (double)eps) + (double)eps));
 }
 
+// d sisdr_b / d src[n] = p_b tar[n] + q_b src[n] for n < lengths[b] (evaluation.py:5-10 differentiated), zeros out to ld.  With a = <s,t>, b = <t,t>,
+// c = <s,s> (the sums se_sisdr_f32 left), alpha = a / (b + eps), E = alpha^2 b, Q = E - 2 alpha a + c + eps, u = E / Q + eps, k = 10 / (ln 10 u):
+//   d alpha = t / (b + eps);  dE = 2 alpha b d alpha;  dQ = (2 alpha b - 2 a) d alpha - 2 alpha t + 2 s
+//   p = k (e1 / Q - E (r1 - 2 alpha) / Q^2),  q = -2 k E / Q^2,   e1 = 2 alpha b / (b + eps),  r1 = (2 alpha b - 2 a) / (b + eps)
+__global__ __launch_bounds__(256) void sisdr_grad_kernel(const float* __restrict__ src, const float* __restrict__ tar, int ld,
+                                                         const int64_t* __restrict__ lengths, float eps, const double* __restrict__ sums,
+                                                         float grad_scale, float* __restrict__ grad) {
+  const int b = blockIdx.y;
+  const int64_t L = lengths ? (lengths[b] < ld ? lengths[b] : ld) : ld;
+  const double a = sums[b * 3 + 0], bb = sums[b * 3 + 1], c = sums[b * 3 + 2], e = (double)eps;
+  const double alpha = a / (bb + e);
+  const double E = alpha * alpha * bb;
+  double err = E - 2.0 * alpha * a + c;
+  if (err < 0.0) err = 0.0;
+  const double Q = err + e;
+  const double k = 10.0 / (2.302585092994046 * (E / Q + e));
+  const double e1 = 2.0 * alpha * bb / (bb + e), r1 = (2.0 * alpha * bb - 2.0 * a) / (bb + e);
+  const float p = (float)((double)grad_scale * k * (e1 / Q - E * (r1 - 2.0 * alpha) / (Q * Q)));
+  const float q = (float)((double)grad_scale * k * (-2.0 * E / (Q * Q)));
+  const float* s = src + (size_t)b * ld;
+  const float* t = tar + (size_t)b * ld;
+  float* g = grad + (size_t)b * ld;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < ld; i += (int64_t)gridDim.x * 256)
+    g[i] = (i < L) ? fmaf(p, t[i], q * s[i]) : 0.f;
+}
+
 }  // namespace se
+
+extern "C" int se_sisdr_grad_f32(const float* src, const float* tar, int ld, const int64_t* lengths, int B, float eps, const double* sums,
+                                 float grad_scale, float* grad, void* stream) {
+  SE_REQUIRE(src && tar && sums && grad && B > 0 && B <= 65535 && ld > 0, "se_sisdr_grad_f32: bad argument");
+  const int chunks = std::max(1, std::min(64, (ld + 2047) / 2048));
+  hipLaunchKernelGGL(se::sisdr_grad_kernel, dim3(chunks, B), dim3(256), 0, se::as_stream(stream), src, tar, ld, lengths, eps, sums, grad_scale, grad);
+  SE_LAUNCH_CHECK();
+  return SE_OK;
+}
 
 extern "C" int se_mix_f32(const float* speech, int ld_s, const int64_t* len_s, const float* noise, int ld_n, const int64_t* len_n,
                           const int64_t* off_n, const float* snr_db, int B, int T_out, int normalize, float target_level_db, float eps,

@@ -75,6 +75,26 @@ inline IstftgShape istftg_shape(int m, int hop) {
   s.lds = (size_t)16 * s.bufN + tables;
   return s;
 }
+
+// the adjoint of the inverse transform (istftg_bwd.hip): FR frames per workgroup; their output elements (FR (m + 1)) and the gradient samples
+// they cover ((FR - 1) hop + n_fft) both fit kGFillIters register slots per thread, and the LDS stays within the forward's 48 KB
+struct IstftgBwdShape {
+  int FR, S, bufN;
+  size_t lds;
+};
+
+inline IstftgBwdShape istftg_bwd_shape(int m, int hop) {
+  const int cap = kGThreads * kGFillIters;
+  IstftgBwdShape s;
+  s.S = fftg_row_stride(m);
+  auto lds = [&](int FR) { return (size_t)16 * ((FR * s.S + 1) & ~1) + (size_t)32 * m; };      // two buffers; twiddles, window, window^2
+  int FR = std::min(32, cap / (m + 1));
+  while (FR > 1 && ((FR - 1) * hop + 2 * m > cap || lds(FR) > kGFwdLds)) --FR;
+  s.FR = FR;
+  s.bufN = (FR * s.S + 1) & ~1;
+  s.lds = lds(FR);
+  return s;
+}
 }  // namespace se
 
 struct se_plan {
@@ -100,6 +120,10 @@ struct se_plan {
   se::FftgSchedule sched = {};
   se::StftgShape fwd = {};
   se::IstftgShape inv = {};
+  // ---- the adjoint iSTFT (se_istft_bwd_f32) runs on the general tables for BOTH plan kinds: a plan of se_plan_create builds m, n_fft, sched,
+  //      g_window, g_window_sq, g_tw and g_rtw for its geometry in a blob of their own (d_blob_g) at creation and stays `general == false`
+  se::IstftgBwdShape bwd = {};
+  void* d_blob_g = nullptr;
   float* g_window = nullptr;       // [n_fft]  forward window
   float* g_window_inv = nullptr;   // [n_fft]  window / m (the inverse transform's scale folded in)
   float* g_window_sq = nullptr;    // [n_fft]  window^2

@@ -151,6 +151,41 @@ extern "C" int se_plan_create(const se_geometry* geom, se_plan** out) {
   SE_HIP(hipMemcpy(p->d_mel_start, mstart.data(), se::kMelMax * 4, hipMemcpyHostToDevice));
   SE_HIP(hipMemcpy(p->d_mel_len, mlen.data(), se::kMelMax * 4, hipMemcpyHostToDevice));
   SE_HIP(hipMemcpy(p->d_mel_w, mw.data(), mw.size() * 4, hipMemcpyHostToDevice));
+  // the general tables of this geometry for the adjoint iSTFT (istftg_bwd.hip); the 400-point kernels never read them
+  {
+    p->m = se::kHalf;
+    p->n_fft = se::kNfft;
+    const int m = p->m, n_fft = p->n_fft;
+    if (!se::fftg_make_schedule(m, &p->sched)) {
+      se_plan_destroy(p);
+      se::set_error("se_plan_create: no radix schedule for m=%d", m);
+      return SE_ERR_UNSUPPORTED;
+    }
+    p->bwd = se::istftg_bwd_shape(m, geom->hop);
+    std::vector<se::cf> tw(m), rtw(m);
+    se::fftg_make_twiddles(m, tw.data(), rtw.data());
+    const size_t o_gw = 0, o_gsq = o_gw + al(4 * n_fft), o_gtw = o_gsq + al(4 * n_fft), o_grtw = o_gtw + al(8 * m), gtotal = o_grtw + al(8 * m);
+    e = hipMalloc(&p->d_blob_g, gtotal);
+    if (e != hipSuccess) {
+      se_plan_destroy(p);
+      return se::hip_fail(e, "hipMalloc(plan tables)", __FILE__, __LINE__);
+    }
+    char* gb = (char*)p->d_blob_g;
+    p->g_window = (float*)(gb + o_gw);
+    p->g_window_sq = (float*)(gb + o_gsq);
+    p->g_tw = (se::cf*)(gb + o_gtw);
+    p->g_rtw = (se::cf*)(gb + o_grtw);
+    struct { void* dst; const void* src; size_t bytes; } copies[] = {
+        {p->g_window, p->h_window.data(), (size_t)4 * n_fft}, {p->g_window_sq, wsq.data(), (size_t)4 * n_fft},
+        {p->g_tw, tw.data(), (size_t)8 * m}, {p->g_rtw, rtw.data(), (size_t)8 * m}};
+    for (auto& c : copies) {
+      e = hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        se_plan_destroy(p);
+        return se::hip_fail(e, "hipMemcpy(plan tables)", __FILE__, __LINE__);
+      }
+    }
+  }
   *out = p;
   return SE_OK;
 }
@@ -206,6 +241,7 @@ extern "C" int se_plan_create_any(const se_geometry* geom, se_plan** out) {
   p->mel_words = (int)csr.size();
   p->fwd = se::stftg_shape(m, p->mel_words);
   p->inv = se::istftg_shape(m, geom->hop);
+  p->bwd = se::istftg_bwd_shape(m, geom->hop);
   if (p->fwd.planeN > p->fwd.bufN || p->fwd.lds > se::kGInvLdsLarge || p->inv.HB < 1 || p->inv.lds > se::kGInvLdsLarge + 1024) {
     delete p;
     se::set_error("se_plan_create_any: no launch shape for m=%d hop=%d within the LDS", m, geom->hop);
@@ -264,6 +300,7 @@ extern "C" int se_plan_chunk_frames(const se_plan* plan, int inverse) {
 extern "C" void se_plan_destroy(se_plan* plan) {
   if (!plan) return;
   if (plan->d_blob) (void)hipFree(plan->d_blob);
+  if (plan->d_blob_g) (void)hipFree(plan->d_blob_g);
   delete plan;
 }
 

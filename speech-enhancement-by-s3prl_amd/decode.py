@@ -1,6 +1,8 @@
 """Rows D1-D2: length masks, masked dB normalisation and Runner._decode_wav (runner.py:216-220,266-270;
 utils.py:26-46) on the gfx950 kernels.  The iSTFT launch already accumulates the masked sum of squares,
-so decode_wav is: se_istft_f32 (+ se_masked_sumsq_f32 of the reference wav) + se_dbnorm_f32."""
+so decode_wav is: se_istft_f32 (+ se_masked_sumsq_f32 of the reference wav) + se_dbnorm_f32.
+With grad mode on and an input that requires grad the same launches run inside autograd nodes (backward: se_istft_bwd_f32, se_dbnorm_bwd_f32),
+so a head can be trained against a loss on the decoded waveform (objective.WavSISDR)."""
 import torch
 
 from . import _lib
@@ -29,9 +31,45 @@ def masked_sumsq(x, lengths):
     return sums
 
 
-def masked_normalize_decibel(audio, target, lengths, eps=1e-8, audio_sumsq=None, inplace=False, ref_sumsq=None):
+class _DbNormFn(torch.autograd.Function):
+    """masked_normalize_decibel as an autograd node: forward = the launches of the no-grad path (in place when asked to); backward =
+    se_dbnorm_bwd_f32, which differentiates the scale through the waveform's own masked square sum.  No gradient flows to a reference waveform."""
+
+    @staticmethod
+    def forward(ctx, audio, target, lengths, eps, audio_sumsq, inplace, ref_sumsq):
+        if inplace:
+            ctx.mark_dirty(audio)
+        ctx.args = []
+        out = masked_normalize_decibel(audio, target, lengths, eps, audio_sumsq, inplace, ref_sumsq, _sums_out=ctx.args)      # grad mode is off in here
+        lens, wav_sumsq, ref_sumsq, ctx.fixed = ctx.args
+        ctx.eps, ctx.has_ref = float(eps), ref_sumsq is not None
+        ctx.save_for_backward(out, lens, wav_sumsq, *([ref_sumsq] if ctx.has_ref else []))
+        del ctx.args
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        y, lens, wav_sumsq = ctx.saved_tensors[:3]
+        ref_sumsq = ctx.saved_tensors[3] if ctx.has_ref else None
+        B, T = y.shape
+        g = grad_out.contiguous().float()
+        grad_wav = torch.empty_like(g)
+        scratch = torch.empty(B, device=y.device, dtype=torch.float64)
+        _lib.check(lib.se_dbnorm_bwd_f32(_lib.ptr(y), _lib.ptr(g), B, T, T, _lib.ptr(lens), _lib.ptr(wav_sumsq), _lib.ptr(ref_sumsq), ctx.fixed, ctx.eps,
+                                         _lib.ptr(scratch), _lib.ptr(grad_wav), _lib.stream()), 'se_dbnorm_bwd_f32')
+        return grad_wav, None, None, None, None, None, None
+
+
+def masked_normalize_decibel(audio, target, lengths, eps=1e-8, audio_sumsq=None, inplace=False, ref_sumsq=None, _sums_out=None):
     """utils.py:31-46 with the mask given as lengths (the reference builds it from lengths, runner.py:269).
-    target: number (fixed dB) or reference audio (B, T)."""
+    target: number (fixed dB) or reference audio (B, T).  Differentiable in `audio` (grad mode on, audio.requires_grad)."""
+    if torch.is_grad_enabled() and audio.requires_grad:
+        if not audio.is_cuda:
+            raise _lib.SEError('libse_amd kernels take device tensors only (got a CPU tensor); there is no CPU fallback')
+        if audio.dtype != torch.float32 or not audio.is_contiguous():
+            audio, inplace = audio.contiguous().float(), False
+        return _DbNormFn.apply(audio, target, lengths, eps, audio_sumsq, inplace, ref_sumsq)
     lib = _lib.load()
     audio = audio.contiguous().float()
     if not inplace:
@@ -60,6 +98,8 @@ def masked_normalize_decibel(audio, target, lengths, eps=1e-8, audio_sumsq=None,
         raise NotImplementedError('per-utterance dB tensor targets are unused by the reference')
     _lib.check(lib.se_dbnorm_f32(_lib.ptr(audio), B, T, T, _lib.ptr(lengths), _lib.ptr(audio_sumsq), _lib.ptr(ref_sumsq),
                                  fixed, float(eps), _lib.stream()), 'se_dbnorm_f32')
+    if _sums_out is not None:          # _DbNormFn: what the backward needs of this call
+        _sums_out.extend([lengths, audio_sumsq, ref_sumsq, fixed])
     return audio
 
 

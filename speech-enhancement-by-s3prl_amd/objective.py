@@ -190,3 +190,51 @@ class WSD(nn.Module):
         lens = _frame_lengths(stft_length_masks, stft_lengths, offset.device)
         loss = _WSDFn.apply(linear_inp, offset, linear_tar, lens, self.alpha, self.db_interval, self.eps, self.reduce_fn, self.max_reduce_fn)
         return loss, {}
+
+
+class _WavSISDRFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wav_predicted, wav_tar, lens, eps, reduce_fn):
+        lib = _lib.load()
+        s, t = wav_predicted.contiguous().float(), wav_tar.contiguous().float()
+        B, ld = s.shape
+        sums = torch.empty(3 * B, device=s.device, dtype=torch.float64)
+        sisdr = torch.empty(B, device=s.device, dtype=torch.float32)
+        _lib.check(lib.se_sisdr_f32(_lib.ptr(s), _lib.ptr(t), ld, _lib.ptr(lens), B, float(eps), _lib.ptr(sums), _lib.ptr(sisdr), _lib.stream()), 'se_sisdr_f32')
+        grad = None
+        if wav_predicted.requires_grad:      # d (-sisdr_b) / d wav_predicted, zeros past each length
+            grad = torch.empty_like(s)
+            _lib.check(lib.se_sisdr_grad_f32(_lib.ptr(s), _lib.ptr(t), ld, _lib.ptr(lens), B, float(eps), _lib.ptr(sums), -1.0, _lib.ptr(grad),
+                                             _lib.stream()), 'se_sisdr_grad_f32')
+        tot = torch.stack([-sisdr.double().sum(), torch.full((), float(B), device=s.device, dtype=torch.float64)])
+        if reduce_fn is not None:
+            tot = reduce_fn(tot)            # (sum of per-utterance losses, utterance count) across ranks: a global mean over utterances
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0), tot)
+        return (tot[0] / tot[1]).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, tot = ctx.saved_tensors
+        return grad * (g / tot[1].float()), None, None, None, None
+
+
+class WavSISDR(nn.Module):
+    """The waveform criterion the reference declares on `wav_predicted` / `wav_tar` (objective.py:16-45) with the score of evaluation.py:5-10:
+    -mean_b sisdr_b over the first lengths[b] samples of each utterance.  `wants_wav` tells a training step to decode the waveform for it
+    (pipeline.HeadFinetuneStep); the gradient reaches the head through decode.decode_wav."""
+
+    wants_wav = True
+
+    def __init__(self, eps=1e-10, **kwargs):
+        super().__init__()
+        self.eps = eps
+        self.reduce_fn = None   # set by dist.DataParallelStep: (sum, count) all-reduced before dividing
+
+    def forward(self, wav_predicted, wav_tar, lengths, **kwargs):
+        if not (wav_predicted.is_cuda and wav_tar.is_cuda):
+            raise _lib.SEError('libse_amd kernels take device tensors only (got a CPU tensor); there is no CPU fallback')
+        if wav_tar.shape[-1] < wav_predicted.shape[-1]:
+            raise _lib.SEError('wav_tar is shorter than wav_predicted')
+        wav_tar = wav_tar[..., :wav_predicted.shape[-1]]
+        lens = lengths.to(device=wav_predicted.device, dtype=torch.int64).contiguous()
+        return _WavSISDRFn.apply(wav_predicted, wav_tar, lens, self.eps, self.reduce_fn), {}

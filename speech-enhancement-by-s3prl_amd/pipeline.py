@@ -293,7 +293,13 @@ class HeadFinetuneStep:
         with torch.no_grad():
             feats_up, feats_down, lin_inp, ph_inp, lin_tar, ph_tar = self.pre(wavs)
         predicted, res = self.head(features=feats_down, linears=lin_inp)
-        stft_lengths = lengths // self.pre._win_args['hop_length'] + 1
-        loss, _ = self.criterion(predicted=predicted, linear_inp=lin_inp, linear_tar=lin_tar, stft_lengths=stft_lengths, **res)
+        if getattr(self.criterion, 'wants_wav', False):
+            # a time-domain criterion: train through Runner._decode_wav (runner.py:266-270), normalised to the clean waveform's level
+            wav_tar = wavs[:, getattr(self.pre, 'channel_tar', 1), :]
+            wav_predicted = decode.decode_wav(self.pre, predicted, ph_inp, lengths, wav_tar)
+            loss, _ = self.criterion(wav_predicted=wav_predicted, wav_tar=wav_tar, lengths=lengths)
+        else:
+            stft_lengths = lengths // self.pre._win_args['hop_length'] + 1
+            loss, _ = self.criterion(predicted=predicted, linear_inp=lin_inp, linear_tar=lin_tar, stft_lengths=stft_lengths, **res)
         grad_norm, skipped = self.dp.step(loss)
         return loss.detach(), grad_norm, skipped

@@ -79,6 +79,42 @@ class LazyPhase(LazyTensor):
         return r
 
 
+class _IstftFn(torch.autograd.Function):
+    """OnlinePreprocessor.istft_with_sumsq as an autograd node (linear_power = 2, the phase a constant): forward = the launches of the no-grad
+    path, bit for bit; backward = se_istft_bwd_f32 (the adjoint transform; d power = 0 where power <= 0).  The square sums are not
+    differentiable outputs: the level normalisation's backward (se_dbnorm_bwd_f32) differentiates its scale through the waveform itself."""
+
+    @staticmethod
+    def forward(ctx, linears, pre, phases, lengths, out_len, ref):
+        enc = (type(phases) is LazyPhase and phases._tphase is not None and phases._value is None and phases._tphase.device == linears.device)
+        outs = pre.istft_with_sumsq(linears, phases, lengths=lengths, out_len=out_len, ref=ref)      # grad mode is off in here
+        outs = tuple(outs) + (None,) * (3 - len(outs))
+        wav = outs[0]
+        if wav._is_view():      # the (*lead, stride) reshape: a node's output must own its storage for the in-place level normalisation behind it
+            wav = wav._base if wav._base.shape == wav.shape else wav.clone()
+        outs = (wav,) + outs[1:]
+        ctx.pre, ctx.enc = pre, enc
+        ctx.save_for_backward(linears, phases._tphase if enc else phases.to(linears.device).contiguous().float())
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, grad_wav, *_):
+        if grad_wav is None:
+            return (None,) * 6
+        lib = _lib.load()
+        linears, ph = ctx.saved_tensors
+        F, K = linears.shape[-2:]
+        lin = linears.contiguous().float().reshape(-1, F, K)
+        ph = ph.reshape(-1, F, K)
+        B = lin.shape[0]
+        g = grad_wav.contiguous().float().reshape(B, -1)
+        grad_power = torch.empty_like(lin)
+        _lib.check(lib.se_istft_bwd_f32(ctx.pre._plan(lin.device), _lib.ptr(g), g.shape[1], _lib.ptr(lin), None if ctx.enc else _lib.ptr(ph),
+                                        _lib.ptr(ph) if ctx.enc else None, B, F, _lib.ptr(grad_power), _lib.stream()), 'se_istft_bwd_f32')
+        return grad_power.reshape(linears.shape).to(linears.dtype), None, None, None, None, None
+
+
 class OnlinePreprocessor(nn.Module):
     _FEAT_TYPES = ('complx', 'linear', 'phase', 'mel', 'mfcc')
 
@@ -448,6 +484,13 @@ class OnlinePreprocessor(nn.Module):
     def istft_with_sumsq(self, linears, phases, linear_power=2, lengths=None, out_len=None, ref=None):
         """se_istft_f32; with `lengths` also returns the masked sum of squares (fused, for the dB normalisation).  With `ref` (the reference
         waveform of that normalisation) returns (wav, sumsq, ref_sumsq or None): the encoded-phase kernel sums it in the same launch."""
+        if torch.is_grad_enabled() and linears.requires_grad:
+            # training through the decode: the same launches inside an autograd node whose backward is se_istft_bwd_f32
+            if float(linear_power) != 2.0:
+                raise NotImplementedError('the iSTFT is differentiated for linear_power = 2 only')
+            if not linears.is_cuda:
+                raise _lib.SEError('the iSTFT backward takes device tensors only; there is no CPU fallback')
+            return _IstftFn.apply(linears, self, phases, lengths, out_len, ref)[:2 if ref is None else 3]
         linears, home = self._stage(linears)
         if (type(phases) is LazyPhase and phases._tphase is not None and phases._value is None and float(linear_power) == 2.0 and
                 phases._tphase.device == linears.device and home == linears.device):
@@ -475,6 +518,8 @@ class OnlinePreprocessor(nn.Module):
     def _istft_tphase(self, linears, tphase, lengths, out_len, log_input=False, ref=None):
         """se_istft_tphase_f32: X' = sqrt(linears) * (cos, sin)(tphase) -> waveform (+ the masked square sum when `lengths` is given; + the masked
         square sum of `ref` (B, >= out_len), the reference waveform of the level normalisation, in the same launch).  Returns (wav, sumsq[, ref_sumsq])."""
+        if log_input and torch.is_grad_enabled() and linears.requires_grad:
+            raise NotImplementedError('the iSTFT of a log-power plane (log_input) is not differentiated')
         lib = _lib.load()
         lead = linears.shape[:-2]
         F, K = linears.shape[-2:]
