@@ -593,6 +593,30 @@ void se_stoi_plan_destroy(se_stoi_plan* plan);
 size_t se_stoi_workspace_bytes(const se_stoi_plan* plan, int B, int T);
 int se_stoi_f32(const se_stoi_plan* plan, const float* clean, const float* processed, int ld, const int64_t* lengths, int B, int T, int extended,
                 float* stoi_out, int32_t* kept_out, float* tob_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The gradient of that score in the processed signal (the reference's objective.py:16-45 declares `stoi` / `estoi` criteria on wav_predicted /
+ * wav_tar through asteroid's NegSTOILoss; the criterion here is the negative of se_stoi_f32's own score: parity unpinned vs asteroid /
+ * torch_stoi).  grad (B, ld) = grad_scale d stoi_b / d processed[b, :], written for all ld columns; stoi_out (B) is bit-identical to what
+ * se_stoi_f32 writes (the call runs that entry point's launches, then the backward ones).  Conventions:
+ *   constants  the keep mask, the kept-index list and the clean envelopes depend on the clean signal alone and are not differentiated
+ *   score      exactly the derivative of the forward's fp64 arithmetic, every + EPS kept: STOI's min(c y, x clip) passes the gradient through
+ *              the branch that was taken, the scale c = |x| / (|y| + EPS) is differentiated through every y of its row; ESTOI rows or columns
+ *              with s <= 0 contribute 0, as in the forward
+ *   bands      d E / d Y = Y / E, exactly 0 where E == 0 (the power <= 0 convention of se_istft_bwd_f32); bins outside the 15 bands get 0
+ *   transform  the adjoint of the zero-padded one-sided DFT: gv[n] = Re sum_k G_k e^{+2 pi i k n / 512}, n < 256; one-sided bins are
+ *              independent outputs, so nothing is doubled
+ *   frames     window, overlap-add of the per-frame gradients, gather back to the kept source frames through the inverse of the kept-index
+ *              list (source frame -> compact position or -1), window again, sum of the at most two source frames that cover a sample
+ *   resample   gy[m] = sum_n gy10[n] g[n q - m p + L], accumulated in fp64 (skipped at 10000)
+ *   edges      grad[b, m] is exactly 0 for m >= lengths[b]; the whole row is exactly 0 for an utterance with fewer than 30 kept frames
+ *              (its score is the constant 1e-5)
+ *   order      every scatter is written as a gather or a fixed-order fold through the workspace: no floating-point atomics, two calls give
+ *              bit-identical gradients
+ * workspace: se_stoi_grad_workspace_bytes(plan, B, T) bytes (0 for a NULL plan), no clearing needed.  Asynchronous on `stream`, no allocation,
+ * no host sync. */
+size_t se_stoi_grad_workspace_bytes(const se_stoi_plan* plan, int B, int T);
+int se_stoi_grad_f32(const se_stoi_plan* plan, const float* clean, const float* processed, int ld, const int64_t* lengths, int B, int T,
+                     int extended, float grad_scale, float* stoi_out, float* grad /* (B, ld) */, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Recurrent core of the (Bi)LSTM downstream heads (model.py:37-91, nn.LSTM hidden 256).

@@ -154,6 +154,8 @@ SIGNATURES = {
     'se_stoi_plan_destroy': (None, [_P]),
     'se_stoi_workspace_bytes': (c_size_t, [_P, c_int, c_int]),
     'se_stoi_f32': (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    'se_stoi_grad_workspace_bytes': (c_size_t, [_P, c_int, c_int]),
+    'se_stoi_grad_f32': (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
     'se_lstm_fwd_bf16':(c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     'se_lstm_bwd_bf16': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     'se_colsum_bf16': (c_int, [_P, c_int, c_int, c_int, _P, _P]),

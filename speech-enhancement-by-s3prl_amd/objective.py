@@ -238,3 +238,69 @@ class WavSISDR(nn.Module):
         wav_tar = wav_tar[..., :wav_predicted.shape[-1]]
         lens = lengths.to(device=wav_predicted.device, dtype=torch.int64).contiguous()
         return _WavSISDRFn.apply(wav_predicted, wav_tar, lens, self.eps, self.reduce_fn), {}
+
+
+class _StoiFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wav_predicted, wav_tar, lens, sr, extended, reduce_fn):
+        from .evaluation import _stoi_plan
+        lib = _lib.load()
+        s, t = wav_predicted.contiguous().float(), wav_tar.contiguous().float()
+        B, ld = s.shape
+        plan = _stoi_plan(s.device, sr)
+        score = torch.empty(B, device=s.device, dtype=torch.float32)
+        grad = None
+        with torch.cuda.device(s.device):
+            if wav_predicted.requires_grad:      # d (-stoi_b) / d wav_predicted, zeros past each length: the forward's launches, then the backward's
+                nbytes = lib.se_stoi_grad_workspace_bytes(plan, B, ld)
+                ws = torch.empty(max(1, nbytes), device=s.device, dtype=torch.uint8)
+                grad = torch.empty_like(s)
+                _lib.check(lib.se_stoi_grad_f32(plan, _lib.ptr(t), _lib.ptr(s), ld, _lib.ptr(lens), B, ld, int(extended), -1.0, _lib.ptr(score),
+                                                _lib.ptr(grad), _lib.ptr(ws), nbytes, _lib.stream()), 'se_stoi_grad_f32')
+            else:
+                nbytes = lib.se_stoi_workspace_bytes(plan, B, ld)
+                ws = torch.empty(max(1, nbytes), device=s.device, dtype=torch.uint8)
+                _lib.check(lib.se_stoi_f32(plan, _lib.ptr(t), _lib.ptr(s), ld, _lib.ptr(lens), B, ld, int(extended), _lib.ptr(score), None, None,
+                                           _lib.ptr(ws), nbytes, _lib.stream()), 'se_stoi_f32')
+        tot = torch.stack([-score.double().sum(), torch.full((), float(B), device=s.device, dtype=torch.float64)])
+        if reduce_fn is not None:
+            tot = reduce_fn(tot)            # (sum of per-utterance losses, utterance count) across ranks: a global mean over utterances
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0), tot)
+        return (tot[0] / tot[1]).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, tot = ctx.saved_tensors
+        return grad * (g / tot[1].float()), None, None, None, None, None
+
+
+class stoi(nn.Module):
+    """objective.py:16-29 (asteroid's NegSTOILoss on wav_predicted / wav_tar) as the negative of the project's own device score:
+    -mean_b stoi_b over the first lengths[b] samples of each utterance, stoi_b what evaluation.stoi_batch returns (csrc/stoi.hip) and its
+    gradient that of csrc/stoi_bwd.hip.  Parity unpinned vs asteroid / torch_stoi.  An utterance with fewer than 30 kept frames scores the
+    constant 1e-5 and has a zero gradient.  `wants_wav` as WavSISDR: pipeline.HeadFinetuneStep decodes the waveform for it."""
+
+    wants_wav = True
+    extended = False
+
+    def __init__(self, sr=16000, **kwargs):
+        super().__init__()
+        self.sr = sr
+        self.reduce_fn = None   # set by dist.DataParallelStep: (sum, count) all-reduced before dividing
+
+    def forward(self, wav_predicted, wav_tar, lengths=None, length_masks=None, **kwargs):
+        if not (wav_predicted.is_cuda and wav_tar.is_cuda):
+            raise _lib.SEError('libse_amd kernels take device tensors only (got a CPU tensor); there is no CPU fallback')
+        if wav_tar.shape[-1] < wav_predicted.shape[-1]:
+            raise _lib.SEError('wav_tar is shorter than wav_predicted')
+        wav_tar = wav_tar[..., :wav_predicted.shape[-1]]
+        if lengths is None:      # the reference's signature passes the (B, T) mask
+            lengths = length_masks.sum(dim=-1)
+        lens = lengths.to(device=wav_predicted.device, dtype=torch.int64).contiguous()
+        return _StoiFn.apply(wav_predicted, wav_tar, lens, self.sr, self.extended, self.reduce_fn), {}
+
+
+class estoi(stoi):
+    """objective.py:32-45: the extended form (row- and column-normalised segments), otherwise as `stoi`."""
+
+    extended = True
