@@ -218,6 +218,28 @@ int se_istft_bwd_f32(const se_plan* plan, const float* grad_wav, int wav_stride,
 int se_istft_bwd_chunk_frames(const se_plan* plan);
 
 /*
+ * se_stft_bwd_f32 -- the backward of rows A1 + A2 as se_stft_f32 computes them for one (B, T) waveform (C = 1): the transpose of reflect
+ * padding (m = n_fft / 2 on both sides), framing, window and the one-sided n_fft-point real transform.  One kernel family for both plan kinds
+ * (a plan of se_plan_create runs it on the general tables of its geometry, as se_istft_bwd_f32).
+ *   grad_power  (B, F, K)    d loss / d power     (may be NULL)
+ *   grad_complx (B, F, K, 2) d loss / d (re, im)  (may be NULL; at least one of the two is given)
+ *   complx      (B, F, K, 2) the forward's spectrum X as se_stft_f32 writes it; required iff grad_power is given
+ *   grad_wav    (B, wav_stride): [0, T) fully written (no accumulation), [T, wav_stride) zero-filled
+ *   workspace   >= se_stft_bwd_workspace_bytes(plan, B, T) bytes of device memory; every word read is written inside the call
+ * F = T / hop + 1, K = n_freq, T > n_fft / 2.  With G = grad_complx + 2 grad_power X, N = n_fft and w the window centred in N:
+ *   gy_f[n]     = Re sum_{k = 0..m} G_{f,k} e^{+2 pi i k n / N}     (no doubling of the inner bins; Im G at k = 0 and k = m contributes nothing)
+ *   gpad[p]     = sum_f w[p - hop f] gy_f[p - hop f],  0 <= p < T + 2 m     (overlap-add, no envelope division)
+ *   grad_wav[n] = gpad[n + m] + [1 <= n <= m] gpad[m - n] + [T - 1 - m <= n <= T - 2] gpad[2 (T - 1) + m - n]
+ * (for T <= 2 m both folds can land on one sample).  Asynchronous on `stream`, allocates nothing, no host sync, no floating-point atomics:
+ * repeats are bit-identical.  se_stft_bwd_chunk: padded output samples per workgroup of the kernel (for tests that want to straddle
+ * workgroup borders); -1 for NULL.
+ */
+size_t se_stft_bwd_workspace_bytes(const se_plan* plan, int B, int T);
+int se_stft_bwd_f32(const se_plan* plan, const float* grad_power, const float* grad_complx, const float* complx, int B, int F, int T,
+                    float* grad_wav, int wav_stride, void* workspace, size_t workspace_bytes, void* stream);
+int se_stft_bwd_chunk(const se_plan* plan);
+
+/*
  * se_length_masks_i64 -- row D1: Runner._get_length_masks (runner.py:216-220): masks[b,t] = t < lengths[b] (int64).
  */
 int se_length_masks_i64(const int64_t* lengths, int B, int max_len, int64_t* masks, void* stream);
@@ -659,6 +681,19 @@ int se_wsd_energy_f32(const float* linear_tar, int B, int F, int N, float* energ
 int se_wsd_f32(const float* linear_inp, const float* offset, const float* linear_tar, const int64_t* frame_lengths, const float* energy,
                const float* energy_max, int B, int F, int N, float alpha, float db_interval, float eps, float grad_scale, double* sums,
                float* grad, void* stream);
+
+/* One resolution of objective.MultiResSTFT (spectral convergence + log-magnitude L1, Yamamoto et al. 2020) on two power planes (B, F, K):
+ * |X| = sqrt(max(power_pred, clamp)), |Y| = sqrt(max(power_tar, clamp)); over the bins of the frames f < lengths[b] / hop + 1 (none for
+ * lengths[b] <= 0), lengths (B) int64 waveform lengths on the device:
+ *   loss_b[b] = sqrt(sum (|Y| - |X|)^2) / (sqrt(sum |Y|^2) + 1e-12) + sum |log|Y| - log|X|| / max(count, 1)
+ * se_specdist_loss_f32 leaves the per-utterance fp64 sums and coefficients in scratch (se_specdist_scratch_doubles(B, F, K) doubles, no
+ * clearing needed, no atomics); se_specdist_grad_f32 reads them and writes grad_power_pred (B, F, K) = grad_scale d loss_b / d power_pred, every
+ * element: exactly 0 where power_pred <= clamp, on frames at or past the utterance's count, in the first term when its sum is 0; sign(0) = 0. */
+size_t se_specdist_scratch_doubles(int B, int F, int K);
+int se_specdist_loss_f32(const float* power_pred, const float* power_tar, const int64_t* lengths, int hop, int B, int F, int K, float clamp,
+                         double* scratch, float* loss_b, void* stream);
+int se_specdist_grad_f32(const float* power_pred, const float* power_tar, const int64_t* lengths, int hop, int B, int F, int K, float clamp,
+                         const double* scratch, float grad_scale, float* grad_power_pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optional in-library timing for bench.py's roofline leg: HIP events recorded on the launch stream around

@@ -79,6 +79,9 @@ SIGNATURES = {
     'se_dbnorm_bwd_f32': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P]),
     'se_istft_bwd_f32': (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     'se_istft_bwd_chunk_frames': (c_int, [_P]),
+    'se_stft_bwd_workspace_bytes': (c_size_t, [_P, c_int, c_int]),
+    'se_stft_bwd_f32': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    'se_stft_bwd_chunk': (c_int, [_P]),
     'se_length_masks_i64': (c_int, [_P, c_int, c_int, _P, _P]),
     'se_head_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'se_head_linear_f32': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
@@ -164,6 +167,9 @@ SIGNATURES = {
     'se_sisdr_spec_f32': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
     'se_wsd_energy_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     'se_wsd_f32': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, _P, _P, _P]),
+    'se_specdist_scratch_doubles': (c_size_t, [c_int, c_int, c_int]),
+    'se_specdist_loss_f32': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    'se_specdist_grad_f32': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_float, _P, _P]),
     'se_prof_enable': (c_int, [c_int]),
     'se_prof_reset': (c_int, []),
     'se_prof_read': (c_int, [c_int, POINTER(c_double), POINTER(c_double), POINTER(ctypes.c_longlong)]),

@@ -95,6 +95,31 @@ inline IstftgBwdShape istftg_bwd_shape(int m, int hop) {
   s.lds = lds(FR);
   return s;
 }
+
+// the adjoint of the forward transform (stftg_bwd.hip): a workgroup owns HB hop-blocks of the PADDED gradient (HB hop samples of T + n_fft) and
+// inverse-transforms the FRI = HB + halo frames that reach into that span (halo = floor((n_fft - 1) / hop) frames start before it).  Within
+// the forward's 48 KB where the halo leaves that efficient (HB >= 2 halo), else one workgroup on (almost) the whole LDS, as istftg_shape
+struct StftgBwdShape {
+  int HB, halo, FRI, S, bufN, maxov;
+  size_t lds;
+};
+
+inline StftgBwdShape stftg_bwd_shape(int m, int hop) {
+  StftgBwdShape s;
+  s.S = fftg_row_stride(m);
+  s.halo = (2 * m - 1) / hop;
+  s.maxov = (2 * m + hop - 1) / hop;
+  const size_t tables = (size_t)24 * m;                                     // two twiddle tables, window
+  auto frames = [&](size_t budget) { return (int)((budget - tables) / ((size_t)16 * s.S)); };
+  int FRI = frames(kGFwdLds);
+  if (FRI < 3 * s.halo) FRI = frames(kGInvLdsLarge);
+  FRI = std::min(FRI, 64 + s.halo);
+  s.FRI = FRI;
+  s.HB = FRI - s.halo;
+  s.bufN = (FRI * s.S + 1) & ~1;
+  s.lds = (size_t)16 * s.bufN + tables;
+  return s;
+}
 }  // namespace se
 
 struct se_plan {
@@ -123,6 +148,7 @@ struct se_plan {
   // ---- the adjoint iSTFT (se_istft_bwd_f32) runs on the general tables for BOTH plan kinds: a plan of se_plan_create builds m, n_fft, sched,
   //      g_window, g_window_sq, g_tw and g_rtw for its geometry in a blob of their own (d_blob_g) at creation and stays `general == false`
   se::IstftgBwdShape bwd = {};
+  se::StftgBwdShape sbwd = {};     // the adjoint STFT (se_stft_bwd_f32), on the same tables
   void* d_blob_g = nullptr;
   float* g_window = nullptr;       // [n_fft]  forward window
   float* g_window_inv = nullptr;   // [n_fft]  window / m (the inverse transform's scale folded in)

@@ -162,6 +162,7 @@ extern "C" int se_plan_create(const se_geometry* geom, se_plan** out) {
       return SE_ERR_UNSUPPORTED;
     }
     p->bwd = se::istftg_bwd_shape(m, geom->hop);
+    p->sbwd = se::stftg_bwd_shape(m, geom->hop);
     std::vector<se::cf> tw(m), rtw(m);
     se::fftg_make_twiddles(m, tw.data(), rtw.data());
     const size_t o_gw = 0, o_gsq = o_gw + al(4 * n_fft), o_gtw = o_gsq + al(4 * n_fft), o_grtw = o_gtw + al(8 * m), gtotal = o_grtw + al(8 * m);
@@ -242,7 +243,8 @@ extern "C" int se_plan_create_any(const se_geometry* geom, se_plan** out) {
   p->fwd = se::stftg_shape(m, p->mel_words);
   p->inv = se::istftg_shape(m, geom->hop);
   p->bwd = se::istftg_bwd_shape(m, geom->hop);
-  if (p->fwd.planeN > p->fwd.bufN || p->fwd.lds > se::kGInvLdsLarge || p->inv.HB < 1 || p->inv.lds > se::kGInvLdsLarge + 1024) {
+  p->sbwd = se::stftg_bwd_shape(m, geom->hop);
+  if (p->fwd.planeN > p->fwd.bufN || p->fwd.lds > se::kGInvLdsLarge || p->inv.HB < 1 || p->inv.lds > se::kGInvLdsLarge + 1024 || p->sbwd.HB < 1) {
     delete p;
     se::set_error("se_plan_create_any: no launch shape for m=%d hop=%d within the LDS", m, geom->hop);
     return SE_ERR_UNSUPPORTED;

@@ -304,3 +304,89 @@ class estoi(stoi):
     """objective.py:32-45: the extended form (row- and column-normalised segments), otherwise as `stoi`."""
 
     extended = True
+
+
+class _SpecDistFn(torch.autograd.Function):
+    """One resolution of MultiResSTFT on two power planes: (B) per-utterance losses; backward = the gradient plane the forward's launches wrote
+    (csrc/specdist.hip), scaled per utterance."""
+
+    @staticmethod
+    def forward(ctx, power_pred, power_tar, lens, hop, clamp):
+        lib = _lib.load()
+        p, t = power_pred.contiguous().float(), power_tar.contiguous().float()
+        B, F, K = p.shape
+        scratch = torch.empty(int(lib.se_specdist_scratch_doubles(B, F, K)), device=p.device, dtype=torch.float64)
+        loss_b = torch.empty(B, device=p.device, dtype=torch.float32)
+        _lib.check(lib.se_specdist_loss_f32(_lib.ptr(p), _lib.ptr(t), _lib.ptr(lens), int(hop), B, F, K, float(clamp), _lib.ptr(scratch),
+                                            _lib.ptr(loss_b), _lib.stream()), 'se_specdist_loss_f32')
+        grad = None
+        if power_pred.requires_grad:
+            grad = torch.empty_like(p)
+            _lib.check(lib.se_specdist_grad_f32(_lib.ptr(p), _lib.ptr(t), _lib.ptr(lens), int(hop), B, F, K, float(clamp), _lib.ptr(scratch), 1.0,
+                                                _lib.ptr(grad), _lib.stream()), 'se_specdist_grad_f32')
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0))
+        return loss_b
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return grad * g.float()[:, None, None], None, None, None, None
+
+
+class _UtteranceMeanFn(torch.autograd.Function):
+    """mean over the utterances of (B) per-utterance losses; under data parallelism (sum, count) are all-reduced before dividing"""
+
+    @staticmethod
+    def forward(ctx, loss_b, reduce_fn):
+        tot = torch.stack([loss_b.double().sum(), torch.full((), float(loss_b.numel()), device=loss_b.device, dtype=torch.float64)])
+        if reduce_fn is not None:
+            tot = reduce_fn(tot)
+        ctx.save_for_backward(tot)
+        ctx.n = loss_b.numel()
+        return (tot[0] / tot[1]).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        tot, = ctx.saved_tensors
+        return (g / tot[1].float()).expand(ctx.n), None
+
+
+class MultiResSTFT(nn.Module):
+    """The multi-resolution STFT distance of Yamamoto et al. 2020 (Parallel WaveGAN) between `wav_predicted` and `wav_tar`: at each resolution
+    (n_fft, hop, win) in samples, per utterance, spectral convergence plus the mean log-magnitude L1 over the frames f < lengths[b] // hop + 1,
+    with |X| = sqrt(max(power, clamp)); the loss is the mean over the utterances of the mean over the resolutions.  Both waveforms are zeroed at
+    and past lengths[b] first (the reference's `wav * length_masks`, objective.py:25-26), so the gradient is exactly 0 there.  The transforms
+    run on the general STFT kernels (preprocessor.stft_for_loss; a resolution outside the supported set of se_plan_create_any raises with the
+    plan's message on first use), the gradient flows through se_stft_bwd_f32 and composes with decode.decode_wav.  `wants_wav` as WavSISDR."""
+
+    wants_wav = True
+
+    def __init__(self, resolutions=((256, 64, 256), (512, 128, 512), (1024, 256, 1024)), sample_rate=16000, clamp=1e-7, **kwargs):
+        super().__init__()
+        from .preprocessor import StftPlan
+        self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
+        assert self.resolutions and all(len(r) == 3 for r in self.resolutions)
+        self.sample_rate, self.clamp = sample_rate, float(clamp)
+        self._stfts = [StftPlan(n_fft, hop, win, sample_rate) for n_fft, hop, win in self.resolutions]      # plans: lazily, per device
+        self.reduce_fn = None   # set by dist.DataParallelStep: (sum, count) all-reduced before dividing
+
+    def forward(self, wav_predicted, wav_tar, lengths=None, length_masks=None, **kwargs):
+        from .preprocessor import stft_for_loss
+        if not (wav_predicted.is_cuda and wav_tar.is_cuda):
+            raise _lib.SEError('libse_amd kernels take device tensors only (got a CPU tensor); there is no CPU fallback')
+        if wav_tar.shape[-1] < wav_predicted.shape[-1]:
+            raise _lib.SEError('wav_tar is shorter than wav_predicted')
+        T = wav_predicted.shape[-1]
+        if lengths is None:      # the reference's signature passes the (B, T) mask
+            lengths = length_masks.sum(dim=-1)
+        lens = lengths.to(device=wav_predicted.device, dtype=torch.int64).contiguous()
+        keep = torch.arange(T, device=lens.device)[None, :] < lens[:, None]
+        zero = torch.zeros((), device=lens.device, dtype=wav_predicted.dtype)
+        pred = torch.where(keep, wav_predicted, zero)
+        tar = torch.where(keep, wav_tar[..., :T].to(wav_predicted.dtype), zero).detach()
+        per_res = []
+        for st in self._stfts:
+            hop = st._win_args['hop_length']
+            per_res.append(_SpecDistFn.apply(stft_for_loss(st, pred), stft_for_loss(st, tar), lens, hop, self.clamp))
+        loss_b = torch.stack(per_res).mean(dim=0)
+        return _UtteranceMeanFn.apply(loss_b, self.reduce_fn), {}

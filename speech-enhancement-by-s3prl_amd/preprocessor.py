@@ -115,6 +115,106 @@ class _IstftFn(torch.autograd.Function):
         return grad_power.reshape(linears.shape).to(linears.dtype), None, None, None, None, None
 
 
+class StftPlan:
+    """A bare STFT geometry (n_fft, hop, win in samples) with its lazily created, per-device plans of se_plan_create_any: what a criterion that
+    transforms at resolutions of its own needs (objective.MultiResSTFT), without the buffers and feature lists of an OnlinePreprocessor.
+    Duck-types the three members `stft_for_loss` reads.  A geometry outside the supported set raises with the plan's own message on first use."""
+
+    def __init__(self, n_fft, hop, win, sample_rate=16000, n_mels=40):
+        self._sample_rate = int(sample_rate)
+        self._n_freq, self._n_mels = int(n_fft) // 2 + 1, int(n_mels)
+        self._win_args = {'n_fft': int(n_fft), 'hop_length': int(hop), 'win_length': int(win)}
+        self._plans = {}
+
+    def __getstate__(self):
+        return dict(self.__dict__, _plans={})
+
+    def __deepcopy__(self, memo):
+        return StftPlan(self._win_args['n_fft'], self._win_args['hop_length'], self._win_args['win_length'], self._sample_rate, self._n_mels)
+
+    def __del__(self):
+        try:
+            lib = _lib._lib
+            if lib is not None:
+                for p in self._plans.values():
+                    lib.se_plan_destroy(p)
+        except Exception:
+            pass
+
+    def _plan(self, device):
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        plan = self._plans.get(idx)
+        if plan is None:
+            lib = _lib.load()
+            geom = _lib.Geometry(self._sample_rate, self._win_args['win_length'], self._win_args['hop_length'], self._n_freq, self._n_mels)
+            out = _lib.c_void_p()
+            with torch.cuda.device(idx):
+                _lib.check(lib.se_plan_create_any(geom, out), 'se_plan_create_any')
+            plan = self._plans[idx] = out.value
+        return plan
+
+
+def _stft_planes(pre, wav, want_complx):
+    """se_stft_f32 on a contiguous fp32 (B, T) device waveform -> power (B, F, K)[, complx (B, F, K, 2)]"""
+    lib = _lib.load()
+    B, T = wav.shape
+    F, K = T // pre._win_args['hop_length'] + 1, pre._n_freq
+    power = torch.empty(B, F, K, device=wav.device, dtype=torch.float32)
+    complx = torch.empty(B, F, K, 2, device=wav.device, dtype=torch.float32) if want_complx else None
+    with torch.cuda.device(wav.device):
+        _lib.check(lib.se_stft_f32(pre._plan(wav.device), _lib.ptr(wav), B, 1, T, 0, _lib.ptr(power), None, _lib.ptr(complx), None, _lib.stream()),
+                   'se_stft_f32')
+    return power, complx
+
+
+class _StftFn(torch.autograd.Function):
+    """The analysis transform as an autograd node: forward = se_stft_f32 (power and complx; complx is saved), backward = se_stft_bwd_f32 on
+    whichever of the two outputs received a gradient."""
+
+    @staticmethod
+    def forward(ctx, wav2d, pre):
+        wav = wav2d.contiguous().float()
+        power, complx = _stft_planes(pre, wav, True)
+        ctx.pre, ctx.T, ctx.in_dtype = pre, wav.shape[1], wav2d.dtype
+        ctx.save_for_backward(complx)
+        return power, complx
+
+    @staticmethod
+    def backward(ctx, grad_power, grad_complx):
+        if grad_power is None and grad_complx is None:
+            return None, None
+        lib = _lib.load()
+        complx, = ctx.saved_tensors
+        B, F, K, _ = complx.shape
+        gp = None if grad_power is None else grad_power.contiguous().float()
+        gc = None if grad_complx is None else grad_complx.contiguous().float()
+        dev = complx.device
+        with torch.cuda.device(dev):
+            plan = ctx.pre._plan(dev)
+            nbytes = lib.se_stft_bwd_workspace_bytes(plan, B, ctx.T)
+            ws = torch.empty(max(1, nbytes), device=dev, dtype=torch.uint8)
+            grad_wav = torch.empty(B, ctx.T, device=dev, dtype=torch.float32)
+            _lib.check(lib.se_stft_bwd_f32(plan, _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(complx) if gp is not None else None, B, F, ctx.T,
+                                           _lib.ptr(grad_wav), ctx.T, _lib.ptr(ws), nbytes, _lib.stream()), 'se_stft_bwd_f32')
+        return grad_wav.to(ctx.in_dtype), None
+
+
+def stft_for_loss(pre, wav2d, want_complx=False):
+    """The STFT of a (B, T) device waveform for a criterion: power (B, F, K), or (power, complx (B, F, K, 2)) with want_complx, at the geometry
+    of `pre` (an OnlinePreprocessor or a StftPlan).  A waveform that requires grad goes through an autograd node whose backward is the adjoint
+    transform (se_stft_bwd_f32), so that the result composes with decode.decode_wav; any other input takes the plain forward.  Not a path of
+    OnlinePreprocessor.forward: no features, no phase, no laziness."""
+    if wav2d.dim() != 2:
+        raise ValueError('stft_for_loss takes a (B, T) waveform')
+    if not wav2d.is_cuda:
+        raise _lib.SEError('libse_amd kernels take device tensors only (got a CPU tensor); there is no CPU fallback')
+    if torch.is_grad_enabled() and wav2d.requires_grad:
+        power, complx = _StftFn.apply(wav2d, pre)
+    else:
+        power, complx = _stft_planes(pre, wav2d.detach().contiguous().float(), want_complx)
+    return (power, complx) if want_complx else power
+
+
 class OnlinePreprocessor(nn.Module):
     _FEAT_TYPES = ('complx', 'linear', 'phase', 'mel', 'mfcc')
 
