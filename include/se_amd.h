@@ -357,6 +357,10 @@ size_t se_encoder_workspace_bytes(const se_encoder* enc, int B, int T);
  * se_encoder_fwd_bf16 -- feats (B, T, D) fp32 -> hidden (B, T, H) fp32 (last layer, select_layer -1, eval mode).
  *   lengths (B) int32 device pointer: valid frames per utterance (keys >= length are masked, the
  *   (1-mask)*-10000 additive mask of S3PRL); NULL = all T valid.
+ *   A length of 0 or less (an utterance whose frames are all zero) masks NOTHING: the reference adds -10000 to every score
+ *   of such an utterance, the constant cancels in the softmax, and every query attends to all T keys.  This holds for every
+ *   `lengths` of the attention entries below (se_mhsa_fwd_*, se_mhsa_bwd_bf16, se_mhsa_fwd_x3_*, se_softmax_rows_f32); a length
+ *   above T counts as T.
  *   GEMM operands bf16, fp32 accumulate, fp32 residual stream, fp32 LayerNorm / softmax.
  */
 int se_encoder_fwd_bf16(const se_encoder* enc, const float* feats, const int32_t* lengths, int B, int T,
@@ -372,6 +376,7 @@ int se_encoder_fwd2_bf16(const se_encoder* enc, const float* feats, const uint16
  *                               else:            predicted = act(p), log_predicted = log(p + eps)
  *   hidden (B, T, H) fp32;  predicted, log_predicted (B, T, spec_out) fp32 (either may be NULL);
  *   raw (B, T, spec_out) optional: the un-activated linear output p.
+ *   act: SE_ACT_IDENTITY, SE_ACT_RELU or SE_ACT_SIGMOID; any other id is SE_ERR_INVALID (se_spec_epilogue_f32 too).
  */
 int se_spechead_fwd_bf16(const se_encoder* enc, const float* hidden, int B, int T, int log_target, int act, float eps,
                          float* predicted, float* log_predicted, float* raw,

@@ -352,6 +352,7 @@ extern "C" int se_gelu_layernorm_f32(const float* pre, const float* w, const flo
 extern "C" int se_spec_epilogue_f32(const float* p, size_t n, int log_target, int act, float eps, float* predicted, float* log_predicted,
                                     void* stream) {
   SE_REQUIRE(p && n > 0 && (predicted || log_predicted), "se_spec_epilogue_f32: bad argument");
+  SE_REQUIRE(act == SE_ACT_IDENTITY || act == SE_ACT_RELU || act == SE_ACT_SIGMOID, "se_spec_epilogue_f32: activation %d is not built (Identity / ReLU / Sigmoid)", act);
   const int grid = (int)std::min<size_t>((n + 255) / 256, 8192);
   hipLaunchKernelGGL(se::spec_epilogue_kernel, dim3(grid), dim3(256), 0, se::as_stream(stream), p, n, log_target, act, eps, predicted, log_predicted);
   SE_LAUNCH_CHECK();
@@ -685,6 +686,8 @@ extern "C" int se_spechead_fwd2_bf16(const se_encoder* enc, const float* hidden,
   SE_REQUIRE(enc && hidden && workspace && (predicted || log_predicted || raw), "se_spechead_fwd_bf16: null argument");
   SE_REQUIRE(enc->cfg.spec_out > 0, "se_spechead_fwd_bf16: encoder was created without a spec head");
   SE_REQUIRE(B > 0 && T > 0, "se_spechead_fwd_bf16: bad shape");
+  // the epilogue kernels build Identity / ReLU / Sigmoid only: any other id would silently come out as Identity
+  SE_REQUIRE(act == SE_ACT_IDENTITY || act == SE_ACT_RELU || act == SE_ACT_SIGMOID, "se_spechead_fwd_bf16: activation %d is not built (Identity / ReLU / Sigmoid)", act);
   SE_REQUIRE(workspace_bytes >= se_encoder_workspace_bytes(enc, B, T), "se_spechead_fwd_bf16: workspace too small");
   const int H = enc->cfg.hidden, N = enc->cfg.spec_out;
   const size_t Mz = (size_t)B * T;

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
   const int heads = H / kHD;
   const int q0 = qt * kAQ + wave * 32;
   const int ld = 3 * H;
-  const int len = lengths ? min(max(lengths[b], 1), T) : T;
+  const int len = (lengths && lengths[b] > 0) ? min(lengths[b], T) : T;      // 0 or less: no frame is valid, nothing is masked (the reference's -10000 on every key cancels in the softmax)
   const int nkt = (len + kAK - 1) / kAK;
   const uint16_t* base = qkv + (size_t)b * T * ld + head * kHD;
 
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
   const int heads = H / kHD;
   const int k0 = ktile * kAQ + wave * 32;
   const int ld = 3 * H;
-  const int len = lengths ? min(max(lengths[b], 1), T) : T;
+  const int len = (lengths && lengths[b] > 0) ? min(lengths[b], T) : T;      // 0 or less: no frame is valid, nothing is masked (the reference's -10000 on every key cancels in the softmax)
   const uint16_t* base = qkv + (size_t)b * T * ld + head * kHD;
   const int key = k0 + l31;
   uint16_t* okp = dqkv + ((size_t)b * T + min(key, T - 1)) * ld + H + head * kHD + 4 * hh;

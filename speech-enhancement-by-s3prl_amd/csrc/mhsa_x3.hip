@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   const int q0 = qt * kAQ + wave * 32;
   const int ld = 3 * H;
-  const int len = lengths ? min(max(lengths[b], 1), T) : T;
+  const int len = (lengths && lengths[b] > 0) ? min(lengths[b], T) : T;      // 0 or less: no frame is valid, nothing is masked (the reference's -10000 on every key cancels in the softmax)
   const int nkt = (len + kAK - 1) / kAK;
   const float* base = qkv + (size_t)b * T * ld + head * kHD;
 

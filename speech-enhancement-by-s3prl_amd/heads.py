@@ -72,6 +72,14 @@ def _act_id(name):
     return _lib.SE_ACT[name]
 
 
+def _spec_act_id(name):
+    """the spec-head epilogue kernels (se_spechead_fwd2_bf16, se_spec_epilogue_f32) build Identity / ReLU / Sigmoid only; the C entries reject any other id"""
+    act = _act_id(name)
+    if act not in (_lib.SE_ACT['Identity'], _lib.SE_ACT['ReLU'], _lib.SE_ACT['Sigmoid']):
+        raise NotImplementedError(f"spec head: activation '{name}' is not built (Identity / ReLU / Sigmoid)")
+    return act
+
+
 class Linear(nn.Module):
     """model.py:8-17"""
 
@@ -201,7 +209,7 @@ class SpecHead(nn.Module):
         target_config = ckpt['Settings']['Config']['online']['target']
         self.log = False if 'log' not in target_config else target_config['log']
         self.activation = activation
-        _act_id(activation)
+        _spec_act_id(activation)
         if random_init:
             for param in self.parameters():
                 if param.dim() >= 2:
@@ -216,7 +224,7 @@ class SpecHead(nn.Module):
             from .spechead_train import SpecHeadTrainFn
             predicted, log_predicted = SpecHeadTrainFn.apply(features, sh.dense.weight, sh.dense.bias, sh.LayerNorm.weight, sh.LayerNorm.bias,
                                                              sh.output.weight, sh.output.bias, sh.LayerNorm.variance_epsilon, self.log,
-                                                             _act_id(self.activation), self.eps)
+                                                             _spec_act_id(self.activation), self.eps)
             return predicted, {'log_predicted': log_predicted}
         predicted, log_predicted = sh._engine.spechead(sh, None, features, mode='full', log_target=self.log, act=self.activation, eps=self.eps)
         return predicted, {'log_predicted': log_predicted}
@@ -249,7 +257,7 @@ class Mockingjay(nn.Module):
         target_config = online['target']
         self.log = False if 'log' not in target_config else target_config['log']
         self.activation = activation
-        _act_id(activation)
+        _spec_act_id(activation)
 
     def forward(self, features, **kwargs):
         features = self.mockingjay(features)
@@ -258,7 +266,7 @@ class Mockingjay(nn.Module):
             from .spechead_train import SpecHeadTrainFn
             predicted, log_predicted = SpecHeadTrainFn.apply(features, sh.dense.weight, sh.dense.bias, sh.LayerNorm.weight, sh.LayerNorm.bias,
                                                              sh.output.weight, sh.output.bias, sh.LayerNorm.variance_epsilon, self.log,
-                                                             _act_id(self.activation), self.eps)
+                                                             _spec_act_id(self.activation), self.eps)
             return predicted, {'log_predicted': log_predicted}
         predicted, log_predicted = sh._engine.spechead(sh, None, features, mode='full', log_target=self.log, act=self.activation, eps=self.eps)
         return predicted, {'log_predicted': log_predicted}

@@ -65,10 +65,16 @@ def _flat(t, B, T, heads):
     return t.transpose(1, 2).reshape(B * T, heads * HD)
 
 
+def effective_lengths(lengths, T):
+    """the kernels' rule (include/se_amd.h): a length of 0 or less masks nothing (the reference's -10000 on every key cancels in the softmax), a
+    length above T counts as T"""
+    return None if lengths is None else [T if int(n) <= 0 else min(int(n), T) for n in lengths]
+
+
 def _core(qkv, d_o, lengths, B, T, heads, drop, seed, site, ctx_for_D, keep):
     q, k, v = _split(qkv, B, T, heads)
     g = _rows(d_o, B, T, heads)
-    n = torch.full((B,), T, dtype=torch.long) if lengths is None else torch.as_tensor(lengths).long().clamp(1, T)      # the kernels clamp to [1, T]
+    n = torch.full((B,), T, dtype=torch.long) if lengths is None else torch.as_tensor(effective_lengths(lengths, T))
     s = q @ k.transpose(-1, -2) / 8.0
     s = s.masked_fill((torch.arange(T)[None, :] >= n[:, None])[:, None, None, :], float('-inf'))
     lse = torch.logsumexp(s, dim=-1)

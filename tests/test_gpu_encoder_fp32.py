@@ -144,7 +144,8 @@ def test_split3_terms_reconstruct_the_operand(gpu):
         assert err.max().item() < 2.0 ** -16
 
 
-@pytest.mark.parametrize('B,T,heads,lens', [(2, 333, 3, [333, 130]), (1, 1001, 2, None), (3, 64, 1, [64, 1, 33]), (1, 129, 12, [77])])
+@pytest.mark.parametrize('B,T,heads,lens', [(2, 333, 3, [333, 130]), (1, 1001, 2, None), (3, 64, 1, [64, 1, 33]), (1, 129, 12, [77]),
+                                            (3, 130, 2, [130, 0, 65])])      # a silent utterance: the -10000 on every key cancels, full attention
 def test_mhsa_x3_vs_fp64(gpu, B, T, heads, lens):
     """se_mhsa_fwd_x3_f32 (two-term operand splits, three products each, exact online softmax) against fp64 attention with the reference's
     additive -10000 on padded keys: 3e-5 of the largest context value (the split drops 2^-18-relative product terms)"""

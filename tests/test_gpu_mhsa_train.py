@@ -113,6 +113,7 @@ def _check(tag, out, qkv, d_o, lens, B, T, heads, drop, bounds, floor=None, lse_
     rctx, rlse, rD = R.mhsa_train_ref(qkv, d_o, lens, B, T, heads, drop, SEED, SITE)[:3]
     rdQ, rdK, rdV = R.mhsa_train_ref(qkv, d_o, lens, B, T, heads, drop, SEED, SITE, ctx_for_D=ctx)[3:]
     H = heads * 64
+    lens = R.effective_lengths(lens, T)         # a length of 0 masks nothing: no padded query or key rows in that utterance
     # forward, all q < T (padded queries are ordinary rows)
     e = (lse.double() - rlse).abs()
     assert e.max().item() < lse_tol, (tag, 'lse', e.max().item(), divmod(int(e.argmax()), T))
@@ -147,8 +148,9 @@ def _check(tag, out, qkv, d_o, lens, B, T, heads, drop, bounds, floor=None, lse_
 
 
 SHAPES = {'a': (1, 64, 1, None), 'b': (1, 65, 1, [64]), 'c': (2, 129, 1, [129, 65]), 'd': (R.CASE_D[0], R.CASE_D[1], R.CASE_D[2], list(R.CASE_D[3])),
-          'e': (2, 257, 4, [257, 120]), 'f': (3, 200, 3, [200, 77, 1])}
-CASES = [(c, p) for c in 'abcdef' for p in (0.0, 0.1)] + [('b', 0.5), ('d', 0.5)]      # T odd in (b) and (c): the last pair of a row is half used
+          'e': (2, 257, 4, [257, 120]), 'f': (3, 200, 3, [200, 77, 1]),
+          'g': (3, 130, 2, [130, 0, 65])}      # a silent utterance (length 0): full attention over the T keys, forward and backward
+CASES = [(c, p) for c in 'abcdef' for p in (0.0, 0.1)] + [('b', 0.5), ('d', 0.5), ('g', 0.0), ('g', 0.1)]      # T odd in (b) and (c): the last pair of a row is half used
 
 
 @pytest.mark.parametrize('case,drop', CASES)
